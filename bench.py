@@ -14,6 +14,11 @@ tile-sharded (16x16 tiles, tile t -> rank t mod N), so scaling is STRONG (fixed 
 Rays = closest-hit + shadow traversals per frame, counted by the kernel in an untimed stats
 frame (identical every frame: the keyed RNG makes the frame deterministic).
 
+A plain run sets up, counts the rays, warms up, times the steps and prints the line.  --full adds
+what takes runs of its own: the roofline (reference-order stats frame, serial frames, per-pass and
+per-launch times, the PMC records), the host-output frame, the P3F load leg and the CPU baseline.
+--dump-outputs DIR writes the last timed step's frame to DIR/frame.npy.
+
 Prints ONE JSON line on rank 0.  Launch for N > 1:
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
       --master-port P bench.py --gpus N --steps K --warmup W
@@ -149,6 +154,23 @@ def interval_union(starts, ends):
     return tot
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, frame):
+    """--dump-outputs: the frame of the last timed step as DIR/frame.npy, float32 (res_y, res_x, 3).
+    A frame past 64 MB is written as a fixed sample of its pixels, (n, 3) in ascending pixel index
+    (default_rng(0) over the frame's pixel count, so two runs of the same arguments pick the same)."""
+    frame = np.ascontiguousarray(frame, dtype=np.float32)
+    if frame.nbytes > DUMP_LIMIT_BYTES:
+        px = frame.reshape(-1, 3)
+        pick = np.sort(np.random.default_rng(0).choice(len(px), DUMP_LIMIT_BYTES // 12, replace=False))
+        frame = px[pick]
+    d = Path(out_dir)
+    d.mkdir(parents=True, exist_ok=True)
+    np.save(d / "frame.npy", frame)
+
+
 def load_ceiling():
     """The measured ceilings of the path kernel's access shape (profiles/gather_ceiling.json,
     tools/gather_ceiling.hip): dependent 64-B per-lane record gathers from an L1/L2-resident table
@@ -205,7 +227,17 @@ def main():
                          "scene.cpp:565-594, bvh.cpp:27-227)")
     ap.add_argument("--traffic-json", default=str(ROOT / "profiles" / "pmc_traffic.json"),
                     help="per-launch HBM bytes measured by rocprofv3 --pmc (tools/pmc_traffic.py)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure and report what the headline figure does not need: "
+                         "the roofline (reference-order stats frame, serial frames, per-pass and per-launch times, "
+                         "PMC records), the host-output frame, the P3F load leg and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, rank 0 writes the frame the last timed step rendered to "
+                         "DIR/frame.npy (float32 (res, res, 3); a fixed seeded sample of its pixels, (n, 3), "
+                         "if the frame is larger than 64 MB)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -220,7 +252,7 @@ def main():
     # Started before anything touches the GPU, and not under a profiler (rocprofv3 preloads its
     # library into every child, and with --pmc that library would initialise the GPU in the writer).
     profiled = "rocprof" in os.environ.get("LD_PRELOAD", "")
-    if rank == 0 and args.scene == "synthetic" and not args.no_load_timing and not profiled:
+    if args.full and rank == 0 and args.scene == "synthetic" and not args.no_load_timing and not profiled:
         import subprocess
         import tempfile
 
@@ -317,11 +349,13 @@ def main():
             "wide_verify"]
     # untimed reference-order stats frame (every shadow query on the reference's binary tree, one
     # pass): §8(d)'s algorithmic bytes on the reference tree, the basis of rounds 1-3's roofline
-    step(ref_p)
-    torch.cuda.synchronize()
-    st_ref = r.stats()
-    bytes_ref_tree = NODE_BYTES * (st_ref["closest_inner"] + st_ref["shadow_inner"]) + \
-        PRIM_BYTES * (st_ref["closest_prims"] + st_ref["shadow_prims"])
+    bytes_ref_tree = 0
+    if args.full:
+        step(ref_p)
+        torch.cuda.synchronize()
+        st_ref = r.stats()
+        bytes_ref_tree = NODE_BYTES * (st_ref["closest_inner"] + st_ref["shadow_inner"]) + \
+            PRIM_BYTES * (st_ref["closest_prims"] + st_ref["shadow_prims"])
     mine = torch.tensor([st[k] for k in keys], dtype=torch.float64, device="cuda")
     tot = mine.clone()
     if world > 1:
@@ -370,18 +404,114 @@ def main():
     if world > 1:
         dist.all_reduce(dt_t, op=dist.ReduceOp.MAX)
     dt = float(dt_t.item())
+    if args.dump_outputs and rank == 0:
+        # what the last timed step left in its output buffer, before any later frame reuses it
+        dump_outputs(args.dump_outputs, frames[(args.steps - 1) % pipe].cpu().numpy())
     # roofline.kernel_ms: device time the path kernel held per step over the timed region — the
     # union of the timed frames' path-kernel spans (HIP events on each frame's stream, one device
     # clock) divided by the steps.  Frames in flight overlap, so a single frame's span also holds
     # its wait for the other frame's blocks; the union counts every instant once.
-    try:
-        ps, pe, _ = r.frame_spans(args.steps)
-        kernel_ms = interval_union(ps, pe) / max(1, len(ps))
-    except AttributeError:  # an A/B build (DRT_LIBRARY) older than drt_frame_spans
-        kernel_ms = None
+    kernel_ms = None
+    if args.full:
+        try:
+            ps, pe, _ = r.frame_spans(args.steps)
+            kernel_ms = interval_union(ps, pe) / max(1, len(ps))
+        except AttributeError:  # an A/B build (DRT_LIBRARY) older than drt_frame_spans
+            kernel_ms = None
+    frame_check = None
+    if args.check_frame:
+        step(shard_p)  # assemble one more frame, then compare it with a one-shot whole frame
+        torch.cuda.synchronize()
+        if rank == 0:
+            whole = torch.empty_like(frame)
+            r.render_device(r.frame_params(seed=args.seed, **fkw), whole.data_ptr(), sptr)
+            torch.cuda.synchronize()
+            frame_check = bool(torch.equal(whole.view(torch.int32), frame.view(torch.int32)))
+        if world > 1:
+            dist.barrier()
+    bytes_launch = NODE_BYTES * (mine["closest_inner"] + mine["shadow_inner"]) + \
+        PRIM_BYTES * (mine["closest_prims"] + mine["shadow_prims"] + mine["wide_prims"]) + \
+        WIDE_BYTES * mine["wide_inner"] + LEAFBOX_BYTES * mine["wide_verify"]
+    dflt = {"aperture": 0.0, "focal": 1.0, "roughness": 0.0, "max_depth": 4, "light_spp": 1, "accel": "bvh", "ks": 0.5}
+    extras = [f"{k}{v if isinstance(v, str) else format(v, 'g')}" for k, v in ext.items() if v != dflt[k]]
+    head = f"tris{args.tris}" if args.scene == "synthetic" else args.scene
+    workload_key = "_".join([f"{head}_res{args.res}_spp{args.spp}"] + extras)
+    value = rays_frame * args.steps / dt / 1e6
+    out = {
+        "metric": "Mrays/s + frame ms at 512x512x64spp, 1M-tri BVH scene, 1/2/4/8 MI355X",
+        "value": round(value, 2),
+        "unit": "Mrays/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(dt / args.steps * 1e3, 3),
+        "higher_is_better": True,
+        "scaling": "strong",
+        "vs_baseline": None,
+        "dtype": "f32",
+        "data": ("synthetic (seeded random triangle soup, SURVEY.md §8d)" if args.scene == "synthetic" else
+                 "balls_low scene (reference P3F content, tests/scenegen.py)"),
+        "config": {"workload": (f"synthetic {args.tris} triangles + floor" if args.scene == "synthetic" else
+                                "P3D_Scenes balls_low (10 spheres + plane)")
+                               + f", {args.accel.upper()}, {args.res}x{args.res}, {args.spp} spp, MAX_DEPTH {args.max_depth}, "
+                               + ("1 quad + 1 point light" if args.scene == "synthetic" else "2 quad + 1 point light")
+                               + (f", DoF aperture {args.aperture:g} focal {args.focal:g}" if args.aperture else "")
+                               + (f", roughness {args.roughness:g}" if args.roughness else "")
+                               + (f", {args.light_spp} quad-light samples" if args.light_spp > 1 else ""),
+                   "scene": args.scene, "tris": args.tris if args.scene == "synthetic" else 0, "res": args.res, "spp": args.spp, "accel": args.accel, "key": workload_key,
+                   "parallelism": f"tile-shard x{world}" + (" + RCCL all-gather" if world > 1 else ""),
+                   "frames_in_flight": pipe, "settle_frames": settle},
+        **({"frame_check_vs_whole_frame": frame_check} if args.check_frame else {}),
+        "rays_per_frame": int(rays_frame),
+        "samples_per_frame": int(tot["samples"]),
+        "msamples_per_s": round(tot["samples"] * args.steps / dt / 1e6, 2),
+        "bytes_per_ray": round(bytes_launch / max(1.0, mine["closest_rays"] + mine["shadow_rays"]), 1),
+        "node_visits_per_ray": round((tot["closest_inner"] + tot["shadow_inner"] + tot["closest_leaf"] +
+                                      tot["shadow_leaf"] + tot["wide_inner"] + tot["wide_leaf"]) / max(1.0, rays_frame), 2),
+        # shadow queries on the 4-ary shadow tree (DESIGN.md §4): their share and records per query
+        "shadow_tree": {"share": round(tot["wide_shadow_rays"] / max(1.0, tot["shadow_rays"]), 4),
+                        "inner_per_query": round(tot["wide_inner"] / max(1.0, tot["wide_shadow_rays"]), 2),
+                        "leaf_per_query": round(tot["wide_leaf"] / max(1.0, tot["wide_shadow_rays"]), 2),
+                        "prims_per_query": round(tot["wide_prims"] / max(1.0, tot["wide_shadow_rays"]), 2),
+                        "verify_per_query": round(tot["wide_verify"] / max(1.0, tot["wide_shadow_rays"]), 3)},
+        "setup_s": round(build_s, 2),  # scene from in-memory triangles + BVH build (the P3F path: "load")
+        # fraction of lanes doing useful work in the node loop / in the path loop (wave64)
+        # (Grid: a wave iteration also walks empty cells, several per lane, so visits per wave
+        # iteration is not a lane fraction there; tools/grid_diag.py has the Grid's own counters)
+        "simd_eff": {"node_loop": round((tot["closest_inner"] + tot["shadow_inner"] + tot["closest_leaf"] +
+                                         tot["shadow_leaf"] + tot["wide_inner"] + tot["wide_leaf"] + tot["wide_verify"])
+                                        / max(1.0, 64 * tot["wave_node_iters"]), 3)
+                     if args.accel != "grid" else None,
+                     "path_loop": round(tot["lane_path_iters"] / max(1.0, 64 * tot["wave_path_iters"]), 3),
+                     # BVH leaf block only (the Grid stepper has no separate leaf block)
+                     "leaf_block": round((tot["closest_leaf"] + tot["shadow_leaf"] + tot["wide_leaf"]) /
+                                         (64 * tot["wave_leaf_iters"]), 3) if tot["wave_leaf_iters"] else None},
+        # traversal-stack pushes per ray and the share that went past the LDS part (scratch)
+        "stack": {"pushes_per_ray": round(tot["stack_pushes"] / max(1.0, rays_frame), 2),
+                  "spill_frac": round(tot["stack_spills"] / max(1.0, tot["stack_pushes"]), 4)},
+        # share of the persistent kernel's wave cycles per loop section (stats frame)
+        "cycle_share": {k: round(tot["cycles_" + k] / max(1.0, tot["cycles_refill"] + tot["cycles_node"] +
+                                                           tot["cycles_shade"]), 3)
+                        for k in ("refill", "node", "shade")},
+        # share of the node section spent in the leaf (primitive test) block
+        "leaf_share_of_node": round(tot["cycles_leaf"] / max(1.0, tot["cycles_node"]), 3),
+        "leaf_iter_frac": round(tot["wave_leaf_iters"] / max(1.0, tot["wave_node_iters"]), 3),
+        # s_memtime cycles per wave-level iteration (stats frame; stamps cost some cycles themselves)
+        "cycles_per_iter": {"node": round(tot["cycles_node"] / max(1.0, tot["wave_node_iters"]), 1),
+                            "leaf_block": round(tot["cycles_leaf"] / max(1.0, tot["wave_leaf_iters"]), 1),
+                            "shade": round(tot["cycles_shade"] / max(1.0, tot["wave_path_iters"]), 1)},
+    }
+    if not args.full:
+        # a plain run ends here: the line above is all the headline figure needs
+        if rank == 0:
+            print(json.dumps(out), flush=True)
+        r.close()
+        if world > 1:
+            dist.destroy_process_group()
+        return
 
-    # the path kernel of frames rendered one at a time (untimed, after the timed region): its
-    # launch duration alone, for the rocprof per-dispatch average
+    # --full from here on.  The path kernel of frames rendered one at a time (untimed, after the
+    # timed region): its launch duration alone, for the rocprof per-dispatch average
     serial = 3
     for _ in range(serial):
         r.render_device(shard_p, (frames[0] if world == 1 else fgs[0].shard).data_ptr(), sptr)
@@ -397,17 +527,6 @@ def main():
             stage_ms = r.frame_stage_times()
         except (AttributeError, RuntimeError):  # (an A/B build older than drt_frame_stage_times)
             stage_ms = None
-    frame_check = None
-    if args.check_frame:
-        step(shard_p)  # assemble one more frame, then compare it with a one-shot whole frame
-        torch.cuda.synchronize()
-        if rank == 0:
-            whole = torch.empty_like(frame)
-            r.render_device(r.frame_params(seed=args.seed, **fkw), whole.data_ptr(), sptr)
-            torch.cuda.synchronize()
-            frame_check = bool(torch.equal(whole.view(torch.int32), frame.view(torch.int32)))
-        if world > 1:
-            dist.barrier()
     host_frame_ms = None
     if world == 1:
         # PCIe-inclusive variant (not `value`): drt_render with the frame copied to host memory
@@ -418,17 +537,10 @@ def main():
     serial_ms = float(np.mean(path_ms)) if len(path_ms) else float("nan")
     if kernel_ms is None:
         kernel_ms = serial_ms
-    bytes_launch = NODE_BYTES * (mine["closest_inner"] + mine["shadow_inner"]) + \
-        PRIM_BYTES * (mine["closest_prims"] + mine["shadow_prims"] + mine["wide_prims"]) + \
-        WIDE_BYTES * mine["wide_inner"] + LEAFBOX_BYTES * mine["wide_verify"]
     achieved = bytes_launch / (kernel_ms * 1e-3) / 1e9
     ceiling = load_ceiling()
     traffic = None
     valu_busy = None
-    dflt = {"aperture": 0.0, "focal": 1.0, "roughness": 0.0, "max_depth": 4, "light_spp": 1, "accel": "bvh", "ks": 0.5}
-    extras = [f"{k}{v if isinstance(v, str) else format(v, 'g')}" for k, v in ext.items() if v != dflt[k]]
-    head = f"tris{args.tris}" if args.scene == "synthetic" else args.scene
-    workload_key = "_".join([f"{head}_res{args.res}_spp{args.spp}"] + extras)
     tj = Path(args.traffic_json)
     pmc = {}
     read_bytes = None
@@ -532,31 +644,7 @@ def main():
                     if pp.get(k) is not None:
                         row[k] = round(pp[k], 4)
             pass_rows.append(row)
-    value = rays_frame * args.steps / dt / 1e6
-    out = {
-        "metric": "Mrays/s + frame ms at 512x512x64spp, 1M-tri BVH scene, 1/2/4/8 MI355X",
-        "value": round(value, 2),
-        "unit": "Mrays/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": round(dt / args.steps * 1e3, 3),
-        "higher_is_better": True,
-        "scaling": "strong",
-        "vs_baseline": None,
-        "dtype": "f32",
-        "data": ("synthetic (seeded random triangle soup, SURVEY.md §8d)" if args.scene == "synthetic" else
-                 "balls_low scene (reference P3F content, tests/scenegen.py)"),
-        "config": {"workload": (f"synthetic {args.tris} triangles + floor" if args.scene == "synthetic" else
-                                "P3D_Scenes balls_low (10 spheres + plane)")
-                               + f", {args.accel.upper()}, {args.res}x{args.res}, {args.spp} spp, MAX_DEPTH {args.max_depth}, "
-                               + ("1 quad + 1 point light" if args.scene == "synthetic" else "2 quad + 1 point light")
-                               + (f", DoF aperture {args.aperture:g} focal {args.focal:g}" if args.aperture else "")
-                               + (f", roughness {args.roughness:g}" if args.roughness else "")
-                               + (f", {args.light_spp} quad-light samples" if args.light_spp > 1 else ""),
-                   "scene": args.scene, "tris": args.tris if args.scene == "synthetic" else 0, "res": args.res, "spp": args.spp, "accel": args.accel, "key": workload_key,
-                   "parallelism": f"tile-shard x{world}" + (" + RCCL all-gather" if world > 1 else ""),
-                   "frames_in_flight": pipe, "settle_frames": settle},
+    out.update({
         # bound: the per-CU vector-memory path serving dependent 64-B per-lane record gathers (TD
         # busy 98 %), peak = tools/gather_ceiling.hip's L1/L2-resident rate; achieved =
         # algorithmic record bytes (64 B per inner-node visit + 48 B per primitive test) per second
@@ -591,46 +679,7 @@ def main():
                      "pass_sum_ms": round(float(np.mean(pass1_ms) + np.mean(pass2_ms)), 3) if len(pass1_ms) else None,
                      "ceiling": ceiling},
         "host_output_frame_ms": None if host_frame_ms is None else round(host_frame_ms, 3),
-        **({"frame_check_vs_whole_frame": frame_check} if args.check_frame else {}),
-        "rays_per_frame": int(rays_frame),
-        "samples_per_frame": int(tot["samples"]),
-        "msamples_per_s": round(tot["samples"] * args.steps / dt / 1e6, 2),
-        "bytes_per_ray": round(bytes_launch / max(1.0, mine["closest_rays"] + mine["shadow_rays"]), 1),
-        "node_visits_per_ray": round((tot["closest_inner"] + tot["shadow_inner"] + tot["closest_leaf"] +
-                                      tot["shadow_leaf"] + tot["wide_inner"] + tot["wide_leaf"]) / max(1.0, rays_frame), 2),
-        # shadow queries on the 4-ary shadow tree (DESIGN.md §4): their share and records per query
-        "shadow_tree": {"share": round(tot["wide_shadow_rays"] / max(1.0, tot["shadow_rays"]), 4),
-                        "inner_per_query": round(tot["wide_inner"] / max(1.0, tot["wide_shadow_rays"]), 2),
-                        "leaf_per_query": round(tot["wide_leaf"] / max(1.0, tot["wide_shadow_rays"]), 2),
-                        "prims_per_query": round(tot["wide_prims"] / max(1.0, tot["wide_shadow_rays"]), 2),
-                        "verify_per_query": round(tot["wide_verify"] / max(1.0, tot["wide_shadow_rays"]), 3)},
-        "setup_s": round(build_s, 2),  # scene from in-memory triangles + BVH build (the P3F path: "load")
-        # fraction of lanes doing useful work in the node loop / in the path loop (wave64)
-        # (Grid: a wave iteration also walks empty cells, several per lane, so visits per wave
-        # iteration is not a lane fraction there; tools/grid_diag.py has the Grid's own counters)
-        "simd_eff": {"node_loop": round((tot["closest_inner"] + tot["shadow_inner"] + tot["closest_leaf"] +
-                                         tot["shadow_leaf"] + tot["wide_inner"] + tot["wide_leaf"] + tot["wide_verify"])
-                                        / max(1.0, 64 * tot["wave_node_iters"]), 3)
-                     if args.accel != "grid" else None,
-                     "path_loop": round(tot["lane_path_iters"] / max(1.0, 64 * tot["wave_path_iters"]), 3),
-                     # BVH leaf block only (the Grid stepper has no separate leaf block)
-                     "leaf_block": round((tot["closest_leaf"] + tot["shadow_leaf"] + tot["wide_leaf"]) /
-                                         (64 * tot["wave_leaf_iters"]), 3) if tot["wave_leaf_iters"] else None},
-        # traversal-stack pushes per ray and the share that went past the LDS part (scratch)
-        "stack": {"pushes_per_ray": round(tot["stack_pushes"] / max(1.0, rays_frame), 2),
-                  "spill_frac": round(tot["stack_spills"] / max(1.0, tot["stack_pushes"]), 4)},
-        # share of the persistent kernel's wave cycles per loop section (stats frame)
-        "cycle_share": {k: round(tot["cycles_" + k] / max(1.0, tot["cycles_refill"] + tot["cycles_node"] +
-                                                           tot["cycles_shade"]), 3)
-                        for k in ("refill", "node", "shade")},
-        # share of the node section spent in the leaf (primitive test) block
-        "leaf_share_of_node": round(tot["cycles_leaf"] / max(1.0, tot["cycles_node"]), 3),
-        "leaf_iter_frac": round(tot["wave_leaf_iters"] / max(1.0, tot["wave_node_iters"]), 3),
-        # s_memtime cycles per wave-level iteration (stats frame; stamps cost some cycles themselves)
-        "cycles_per_iter": {"node": round(tot["cycles_node"] / max(1.0, tot["wave_node_iters"]), 1),
-                            "leaf_block": round(tot["cycles_leaf"] / max(1.0, tot["wave_leaf_iters"]), 1),
-                            "shade": round(tot["cycles_shade"] / max(1.0, tot["wave_path_iters"]), 1)},
-    }
+    })
     if p3f_writer is not None:  # f1: Scene::load_p3f + BVH::Build of the file (the reference: 65 s)
         try:
             p3f_writer.wait(timeout=300)

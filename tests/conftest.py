@@ -19,13 +19,9 @@ if str(ROOT) not in sys.path:
 # force it at every size (DRT_AA_TWO_PASS=2; test_aa_two_pass_size_rule checks the default rule).
 os.environ.setdefault("DRT_AA_TWO_PASS", "2")
 
-REFERENCE = Path("/root/reference/DistributionRayTracer")
-SCENES = REFERENCE / "P3D_Scenes"
-
 
 def pytest_configure(config):
     config.addinivalue_line("markers", "gpu: requires an MI355X GPU (HIP)")
-    config.addinivalue_line("markers", "reference: requires the reference checkout at /root/reference")
     config.addinivalue_line("markers", "slow: long-running CPU test")
 
 
@@ -35,10 +31,3 @@ def oracle_mod():
 
     O.build()
     return O
-
-
-def have_reference():
-    return (REFERENCE / "bvh.cpp").exists()
-
-
-needs_reference = pytest.mark.skipif(not have_reference(), reason="reference checkout not present")

@@ -15,7 +15,6 @@ import pytest
 import distributionraytracer_amd as drt
 from distributionraytracer_amd import _lib
 from tests import scenegen as sg
-from tests.conftest import SCENES, needs_reference
 
 ROOT = Path(__file__).resolve().parents[1]
 GOLD = ROOT / "tests" / "golden"
@@ -202,13 +201,16 @@ def test_set_eye_matches_oracle_camera(oracle_mod):
             assert (f.w, f.h, f.aperture) == (f0.w, f0.h, f0.aperture)
 
 
-@needs_reference
 @pytest.mark.parametrize("scene", ["balls_low", "dof", "teste", "motion", "balls_box", "blueDiamond",
                                    "dragon_assignment1"])
-def test_p3f_loader_matches_oracle(oracle_mod, scene):
+def test_p3f_loader_matches_oracle(oracle_mod, tmp_path, scene):
+    from tests import shipped
+
     O = oracle_mod
-    a = drt.Scene.load_p3f(SCENES / f"{scene}.p3f", skybox_max_size=8)
-    b = O.Scene.load_p3f(SCENES / f"{scene}.p3f", skybox_max_size=8)
+    p = shipped.write(tmp_path, scene)  # the shipped file, byte for byte (tests/golden/shipped_scenes.npz)
+    faces = shipped.skybox_faces(scene)
+    a = drt.Scene.load_p3f(p, skybox_faces=faces)
+    b = O.Scene.load_p3f(p, skybox_faces=faces)
     ia, ib = a.info(), b.info()
     for k in ("res_x", "res_y", "spp", "accel", "n_objects", "n_lights", "n_materials", "has_env"):
         assert getattr(ia, k) == getattr(ib, k), k

@@ -9,7 +9,7 @@ if [ $rc -ge 2 ]; then exit $rc; fi
 i=0
 for v in "$@"; do
   i=$((i+1))
-  env $v timeout -k 10 300 python bench.py --steps ${STEPS:-3} --warmup 1 --no-cpu-baseline > $OUT/ab_$i.json 2> $OUT/ab_$i.err
+  env $v timeout -k 10 300 python bench.py --full --steps ${STEPS:-3} --warmup 1 --no-cpu-baseline > $OUT/ab_$i.json 2> $OUT/ab_$i.err
   rc=$?
   python - "$v" $OUT/ab_$i.json <<'PY'
 import json,sys

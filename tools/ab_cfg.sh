@@ -7,7 +7,7 @@ OUT=gpurun_out; mkdir -p $OUT
 one() {  # lib, name, bench args...
   local lib=$1 name=$2; shift 2
   local envv=""; [ "$lib" != base ] && envv="DRT_LIBRARY=$lib"
-  env $envv timeout -k 10 300 python bench.py --steps ${STEPS:-5} --warmup 1 --no-cpu-baseline "$@" \
+  env $envv timeout -k 10 300 python bench.py --full --steps ${STEPS:-5} --warmup 1 --no-cpu-baseline "$@" \
     > $OUT/abc.json 2> $OUT/abc.err || return $?
   python -c "import json,sys; d=json.load(open('$OUT/abc.json')); print(f\"{'$name':10s} {'$(basename $lib)':24s} {d['value']:8.1f} Mrays/s {d['ms_per_step']:8.2f} ms\")"
 }

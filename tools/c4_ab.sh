@@ -6,7 +6,7 @@ set -u
 export TMPDIR=/tmp
 OUT=gpurun_out; mkdir -p $OUT; : > $OUT/c4_ab.jsonl
 for v in "$@"; do
-  env $v timeout -k 10 300 python bench.py --res ${RES:-1024} --steps ${STEPS:-3} --warmup 1 --spp 64 --aperture 8 \
+  env $v timeout -k 10 300 python bench.py --full --res ${RES:-1024} --steps ${STEPS:-3} --warmup 1 --spp 64 --aperture 8 \
       --focal 1 --max-depth 8 --roughness 0.1 --no-cpu-baseline > $OUT/c4_ab_run.json 2> $OUT/c4_ab_run.err
   rc=$?
   python - "$v" $OUT/c4_ab_run.json >> $OUT/c4_ab.jsonl <<'PY'

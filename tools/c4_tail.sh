@@ -8,7 +8,7 @@ export TMPDIR=/tmp
 OUT=gpurun_out; mkdir -p $OUT; : > $OUT/c4_tail.jsonl
 C4="--spp 64 --aperture 8 --focal 1 --max-depth 8 --roughness 0.1 --no-cpu-baseline --warmup 1"
 for cfg in "--res 1024 --steps 3" "--res 2048 --steps 2" "--res 1024 --steps 3 --frames-in-flight 1"; do
-  timeout -k 10 300 python bench.py $C4 $cfg > $OUT/c4_tail_run.json 2> $OUT/c4_tail_run.err
+  timeout -k 10 300 python bench.py --full $C4 $cfg > $OUT/c4_tail_run.json 2> $OUT/c4_tail_run.err
   rc=$?
   python - "$cfg" $OUT/c4_tail_run.json >> $OUT/c4_tail.jsonl <<'PY'
 import json, sys

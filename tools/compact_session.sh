@@ -11,4 +11,4 @@ STEPS=8 bash tools/lib_matrix.sh 2 "compact||" "markers|DRT_WAVEFRONT_COMPACT=0|
   "c4_compact||--res 1024 --aperture 8 --focal 1 --roughness 0.1 --max-depth 8 --steps 3" \
   "c4_markers|DRT_WAVEFRONT_COMPACT=0|--res 1024 --aperture 8 --focal 1 --roughness 0.1 --max-depth 8 --steps 3" || exit $?
 cp $OUT/lib_matrix.jsonl $OUT/compact_ab.jsonl
-timeout -k 10 300 python bench.py --steps 5 --warmup 1 --no-cpu-baseline --no-load-timing > $OUT/compact_launch.json 2>/dev/null
+timeout -k 10 300 python bench.py --full --steps 5 --warmup 1 --no-cpu-baseline --no-load-timing > $OUT/compact_launch.json 2>/dev/null

@@ -20,20 +20,20 @@ case "${1:-X}" in
   Y)
     PMC_ONLY="c4 c2" PMC_DB=$OUT/pmc_traffic.json bash tools/pmc_configs.sh || exit $?
     CFG_STEPS=10 bash tools/configs.sh || exit $?
-    timeout -k 10 600 python bench.py --steps 20 --warmup 2 > $OUT/bench.json 2> $OUT/bench.err || exit $?
+    timeout -k 10 600 python bench.py --full --steps 20 --warmup 2 > $OUT/bench.json 2> $OUT/bench.err || exit $?
     cut -c1-300 $OUT/bench.json
     timeout -k 10 600 rocprofv3 --kernel-trace --stats -d $OUT/prof -o run --output-format csv -- \
-        python3 bench.py --steps 20 --warmup 2 --no-cpu-baseline > $OUT/prof_bench.json 2> $OUT/prof.err || exit $?
+        python3 bench.py --full --steps 20 --warmup 2 --no-cpu-baseline > $OUT/prof_bench.json 2> $OUT/prof.err || exit $?
     python tools/rocprof_union.py $OUT/prof --steps 20 --warmup 2 --bench-json $OUT/prof_bench.json > $OUT/rocprof_union.json || exit $?
     cat $OUT/rocprof_union.json
     ;;
   Z)  # the head's bench evidence after a change that needs no new PMC records: Y without its PMC passes, plus
       # the multi-rank rehearsal
     CFG_STEPS=10 bash tools/configs.sh || exit $?
-    timeout -k 10 600 python bench.py --steps 20 --warmup 2 > $OUT/bench.json 2> $OUT/bench.err || exit $?
+    timeout -k 10 600 python bench.py --full --steps 20 --warmup 2 > $OUT/bench.json 2> $OUT/bench.err || exit $?
     cut -c1-300 $OUT/bench.json
     timeout -k 10 600 rocprofv3 --kernel-trace --stats -d $OUT/prof -o run --output-format csv -- \
-        python3 bench.py --steps 20 --warmup 2 --no-cpu-baseline > $OUT/prof_bench.json 2> $OUT/prof.err || exit $?
+        python3 bench.py --full --steps 20 --warmup 2 --no-cpu-baseline > $OUT/prof_bench.json 2> $OUT/prof.err || exit $?
     python tools/rocprof_union.py $OUT/prof --steps 20 --warmup 2 --bench-json $OUT/prof_bench.json > $OUT/rocprof_union.json || exit $?
     cat $OUT/rocprof_union.json
     NPROC=2 bash tools/multirank_check.sh || exit $?
@@ -44,10 +44,10 @@ case "${1:-X}" in
     PMC_ONLY="grid" PMC_DB=$OUT/pmc_traffic.json bash tools/pmc_configs.sh || exit $?
     cp $OUT/pmc_traffic.json profiles/pmc_traffic.json
     CFG_STEPS=10 bash tools/configs.sh || exit $?
-    timeout -k 10 600 python bench.py --steps 20 --warmup 2 > $OUT/bench.json 2> $OUT/bench.err || exit $?
+    timeout -k 10 600 python bench.py --full --steps 20 --warmup 2 > $OUT/bench.json 2> $OUT/bench.err || exit $?
     cut -c1-300 $OUT/bench.json
     timeout -k 10 600 rocprofv3 --kernel-trace --stats -d $OUT/prof -o run --output-format csv -- \
-        python3 bench.py --steps 20 --warmup 2 --no-cpu-baseline > $OUT/prof_bench.json 2> $OUT/prof.err || exit $?
+        python3 bench.py --full --steps 20 --warmup 2 --no-cpu-baseline > $OUT/prof_bench.json 2> $OUT/prof.err || exit $?
     python tools/rocprof_union.py $OUT/prof --steps 20 --warmup 2 --bench-json $OUT/prof_bench.json > $OUT/rocprof_union.json || exit $?
     cat $OUT/rocprof_union.json
     ;;

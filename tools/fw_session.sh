@@ -14,5 +14,5 @@ cp $OUT/lib_matrix.jsonl $OUT/fw_ab.jsonl
 # per-launch times of the last serial frame (bench.py roofline.passes launches)
 for v in def fw; do
   e=""; [ $v = fw ] && e=$FW
-  env $e timeout -k 10 300 python bench.py --steps 5 --warmup 1 --no-cpu-baseline --no-load-timing > $OUT/fw_launch_$v.json 2>/dev/null || exit $?
+  env $e timeout -k 10 300 python bench.py --full --steps 5 --warmup 1 --no-cpu-baseline --no-load-timing > $OUT/fw_launch_$v.json 2>/dev/null || exit $?
 done

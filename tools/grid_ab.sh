@@ -17,7 +17,7 @@ for rep in $(seq ${REPS:-2}); do
     i=$((i+1))
     lib=${v%%|*}; envs=${v#*|}
     envv=""; [ "$lib" != base ] && envv="DRT_LIBRARY=$PWD/distributionraytracer_amd/csrc/$lib"
-    env $envv $envs timeout -k 10 300 python bench.py --accel grid --steps ${STEPS:-5} --warmup 1 --no-cpu-baseline \
+    env $envv $envs timeout -k 10 300 python bench.py --full --accel grid --steps ${STEPS:-5} --warmup 1 --no-cpu-baseline \
       > $OUT/gab_$i.json 2> $OUT/gab_$i.err
     rc=$?
     python - "$v" $OUT/gab_$i.json <<'PY'

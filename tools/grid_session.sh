@@ -16,7 +16,7 @@ CNT="SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VALU_ADD
 for cfg in "bvh:" "grid:--accel grid"; do
   name=${cfg%%:*}; args=${cfg#*:}
   timeout -s KILL 120 rocprofv3 --kernel-trace --pmc $CNT -d $OUT/pmc_f64/$name -o run --output-format csv -- \
-    python3 bench.py --steps 1 --warmup 0 --settle-s 0 --no-cpu-baseline --no-load-timing $args > $OUT/pmc_f64_$name.json 2> $OUT/pmc_f64_$name.err
+    python3 bench.py --full --steps 1 --warmup 0 --settle-s 0 --no-cpu-baseline --no-load-timing $args > $OUT/pmc_f64_$name.json 2> $OUT/pmc_f64_$name.err
   rc=$?; echo "pmc f64 $name rc=$rc"; [ $rc -eq 0 ] || exit $rc
 done
 python3 tools/pmc_passes.py $OUT/pmc_f64/bvh > $OUT/pmc_f64_bvh_kernels.json && python3 tools/pmc_passes.py $OUT/pmc_f64/grid > $OUT/pmc_f64_grid_kernels.json

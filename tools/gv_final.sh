@@ -11,13 +11,13 @@ rc=$?; echo "grid-tree tests rc=$rc"; tail -2 $OUT/gv_tests.log
 : > $OUT/gv_ab.jsonl
 for rep in 1 2; do
   for v in DRT_GRID_TREE_REFILL_MIN=16 DRT_GRID_TREE_REFILL_MIN=24 DRT_GRID_TREE_REFILL_MIN=20; do
-    env $v timeout -k 10 300 python bench.py --accel grid --steps 5 --warmup 1 --no-cpu-baseline \
+    env $v timeout -k 10 300 python bench.py --full --accel grid --steps 5 --warmup 1 --no-cpu-baseline \
       > $OUT/gv_ab.json 2> $OUT/gv_ab.err || { tail -20 $OUT/gv_ab.err; exit 1; }
     python -c "import json,sys; d=json.load(open('$OUT/gv_ab.json')); print(json.dumps({'variant': '$v', 'value': d['value'], 'ms_per_step': d['ms_per_step']}))" >> $OUT/gv_ab.jsonl
     tail -1 $OUT/gv_ab.jsonl
   done
 done
-timeout -k 10 300 python bench.py --accel grid --steps 10 --warmup 1 --cpu-seconds 8 > $OUT/cfg_headline_grid.json \
+timeout -k 10 300 python bench.py --full --accel grid --steps 10 --warmup 1 --cpu-seconds 8 > $OUT/cfg_headline_grid.json \
   2> $OUT/cfg_headline_grid.err
 rc=$?; echo "grid config rc=$rc $(cut -c1-200 $OUT/cfg_headline_grid.json)"
 exit $rc

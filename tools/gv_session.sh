@@ -18,7 +18,7 @@ fi
 : > $OUT/gv_ab.jsonl
 for rep in 1 2; do
   for v in "DRT_GRID_SHADOW_TREE=1" "DRT_GRID_SHADOW_TREE=0"; do
-    env $v timeout -k 10 300 python bench.py --accel grid --steps ${STEPS:-5} --warmup 1 --no-cpu-baseline \
+    env $v timeout -k 10 300 python bench.py --full --accel grid --steps ${STEPS:-5} --warmup 1 --no-cpu-baseline \
       > $OUT/gv_ab.json 2> $OUT/gv_ab.err
     rc=$?
     [ $rc -eq 0 ] || { tail -20 $OUT/gv_ab.err; exit $rc; }
@@ -32,6 +32,6 @@ PY
     tail -1 $OUT/gv_ab.jsonl | cut -c1-200
   done
 done
-timeout -k 10 300 python bench.py --steps ${STEPS:-5} --warmup 1 --no-cpu-baseline > $OUT/gv_bvh.json 2> $OUT/gv_bvh.err
+timeout -k 10 300 python bench.py --full --steps ${STEPS:-5} --warmup 1 --no-cpu-baseline > $OUT/gv_bvh.json 2> $OUT/gv_bvh.err
 rc=$?; echo "bvh headline rc=$rc $(cut -c1-200 $OUT/gv_bvh.json)"
 exit $rc

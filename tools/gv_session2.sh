@@ -4,6 +4,7 @@
 set -u
 export TMPDIR=/tmp
 OUT=gpurun_out; mkdir -p $OUT
+ROOT=$PWD
 timeout -k 10 600 python -u -m pytest tests/test_gpu_grid_tree.py -x -q --timeout 300 --timeout-method thread \
   > $OUT/gv_tests.log 2>&1
 rc=$?; echo "grid-tree tests rc=$rc"; tail -2 $OUT/gv_tests.log
@@ -14,7 +15,7 @@ rc=$?; echo "stats rc=$rc $(cat $OUT/gv_stats.json)"
 : > $OUT/gv_ab.jsonl
 for rep in 1 2; do
   for v in ${GV_VARIANTS:-"DRT_GRID_SHADOW_TREE=1" "DRT_GRID_TREE_WIDEN_LOG2=-17" "DRT_GRID_SHADOW_TREE=0"}; do
-    env $v timeout -k 10 300 python bench.py --accel grid --steps ${STEPS:-5} --warmup 1 --no-cpu-baseline \
+    env $v timeout -k 10 300 python bench.py --full --accel grid --steps ${STEPS:-5} --warmup 1 --no-cpu-baseline \
       > $OUT/gv_ab.json 2> $OUT/gv_ab.err
     rc=$?
     [ $rc -eq 0 ] || { tail -20 $OUT/gv_ab.err; exit $rc; }
@@ -28,8 +29,8 @@ PY
     tail -1 $OUT/gv_ab.jsonl | cut -c1-160
   done
 done
-cd /tmp && timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $GRAFT_REPO_ROOT/$OUT/gv_prof -o gv -- \
-  python3 $GRAFT_REPO_ROOT/bench.py --accel grid --steps 5 --warmup 1 --no-cpu-baseline > $GRAFT_REPO_ROOT/$OUT/gv_prof.log 2>&1
+cd /tmp && timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $ROOT/$OUT/gv_prof -o gv -- \
+  python3 $ROOT/bench.py --full --accel grid --steps 5 --warmup 1 --no-cpu-baseline > $ROOT/$OUT/gv_prof.log 2>&1
 rc=$?; echo "rocprof rc=$rc"
-find $GRAFT_REPO_ROOT/$OUT/gv_prof -name '*stats*.csv' | head -3
+find $ROOT/$OUT/gv_prof -name '*stats*.csv' | head -3
 exit $rc

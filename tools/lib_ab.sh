@@ -14,7 +14,7 @@ fi
 one() {  # lib name args...
   local lib=$1 name=$2; shift 2
   local envv=""; [ "$lib" != base ] && envv="DRT_LIBRARY=$PWD/distributionraytracer_amd/csrc/$lib"
-  env $envv timeout -k 10 300 python bench.py --steps ${STEPS:-5} --warmup 1 --no-cpu-baseline "$@" > $OUT/lab.json 2> $OUT/lab.err || return $?
+  env $envv timeout -k 10 300 python bench.py --full --steps ${STEPS:-5} --warmup 1 --no-cpu-baseline "$@" > $OUT/lab.json 2> $OUT/lab.err || return $?
   python -c "import json; d=json.load(open('$OUT/lab.json')); print(f\"{'$name':9s} {'$(basename $lib)':18s} {d['value']:8.1f} Mrays/s {d['ms_per_step']:8.2f} ms\", flush=True)"
 }
 for rep in $(seq ${REPS:-2}); do

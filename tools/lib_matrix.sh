@@ -8,7 +8,7 @@ reps=$1; shift
 for rep in $(seq 1 $reps); do
   for spec in "$@"; do
     IFS='|' read -r label envs args <<< "$spec"
-    env $envs timeout -k 10 300 python bench.py --steps ${STEPS:-5} --warmup 1 --no-cpu-baseline --no-load-timing $args \
+    env $envs timeout -k 10 300 python bench.py --full --steps ${STEPS:-5} --warmup 1 --no-cpu-baseline --no-load-timing $args \
       > $OUT/m.json 2> $OUT/m.err
     rc=$?
     python - "$label" "$envs" $OUT/m.json >> $OUT/lib_matrix.jsonl <<'PY'

@@ -7,6 +7,6 @@ export TMPDIR=/tmp
 OUT=gpurun_out; mkdir -p $OUT
 N=${NPROC:-2}
 DRT_DIST_BACKEND=gloo timeout -k 10 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node $N \
-  --master-addr 127.0.0.1 --master-port 29611 bench.py --gpus $N --steps ${STEPS:-2} --warmup 1 --res 256 --spp 16 \
+  --master-addr 127.0.0.1 --master-port 29611 bench.py --full --gpus $N --steps ${STEPS:-2} --warmup 1 --res 256 --spp 16 \
   --check-frame > $OUT/mr$N.json 2> $OUT/mr$N.err
 rc=$?; echo "$N-rank rc=$rc"; cut -c1-300 $OUT/mr$N.json; grep -o "\"frame_check[a-z_]*\": [a-z]*" $OUT/mr$N.json; tail -3 $OUT/mr$N.err; exit $rc

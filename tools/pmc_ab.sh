@@ -14,7 +14,7 @@ for lib in ${LIBS:-base}; do
     d=$OUT/l${li}_p$i; rm -rf $d
     if [ "$lib" = base ]; then unset DRT_LIBRARY; else export DRT_LIBRARY=$PWD/$lib; fi
     timeout -k 10 300 rocprofv3 --kernel-trace --pmc $grp -d $d -o run --output-format csv -- \
-        python3 bench.py --steps 1 --warmup 0 --no-cpu-baseline ${BENCH_ARGS:-} > $d.json 2> $d.err
+        python3 bench.py --full --steps 1 --warmup 0 --no-cpu-baseline ${BENCH_ARGS:-} > $d.json 2> $d.err
     rc=$?; [ $rc -eq 0 ] || { echo "pass $lib ($grp) rc=$rc"; tail -5 $d.err; exit $rc; }
   done
   unset DRT_LIBRARY

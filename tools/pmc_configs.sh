@@ -22,7 +22,7 @@ for cfg in "${CONFIGS[@]}"; do
   for grp in "${GROUPS_[@]}"; do
     i=$((i+1))
     timeout -k 10 240 rocprofv3 --kernel-trace --pmc $grp -d $OUT/$name/p$i -o run --output-format csv -- \
-        python3 bench.py --steps 1 --warmup 0 --settle-s 0 --no-cpu-baseline $args > $OUT/$name/p$i.json 2> $OUT/$name/p$i.err
+        python3 bench.py --full --steps 1 --warmup 0 --settle-s 0 --no-cpu-baseline $args > $OUT/$name/p$i.json 2> $OUT/$name/p$i.err
     rc=$?; echo "$name pass $i rc=$rc"; [ $rc -eq 0 ] || exit $rc
   done
   key=$(python3 -c "import json;print(json.load(open('$OUT/$name/p1.json'))['config']['key'])")

@@ -13,7 +13,7 @@ for v in A B; do
     i=$((i+1))
     if [ $v = B ]; then E="DRT_LIBRARY=$B_LIB"; else E="DRT_NONE=1"; fi
     env $E timeout -k 10 240 rocprofv3 --kernel-trace --pmc $grp -d $OUT/$v/p$i -o run --output-format csv -- \
-        python3 bench.py --steps 1 --warmup 0 --settle-s 0 --no-cpu-baseline --no-load-timing --accel grid \
+        python3 bench.py --full --steps 1 --warmup 0 --settle-s 0 --no-cpu-baseline --no-load-timing --accel grid \
         > $OUT/$v/p$i.json 2> $OUT/$v/p$i.err
     rc=$?; echo "$v pass $i rc=$rc"; [ $rc -eq 0 ] || exit $rc
   done

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Per-kernel counter totals of the LAST frame of a `rocprofv3 --pmc ... --kernel-trace` run of bench.py
-(one frame: --steps 1 --warmup 0 --settle-s 0): for each kernel name, the counters of its last dispatch
+(one frame: --full --steps 1 --warmup 0 --settle-s 0): for each kernel name, the counters of its last dispatch
 (the timed frame's; bench.py's stats frames come first).  Used for the Grid / BVH chain-pass comparison
 (DESIGN.md §7, round 6).
 

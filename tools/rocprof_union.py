@@ -1,10 +1,10 @@
 #!/usr/bin/env python3
-"""Path-kernel device time per step from a rocprofv3 kernel trace of `bench.py --steps K --warmup W`,
+"""Path-kernel device time per step from a rocprofv3 kernel trace of `bench.py --full --steps K --warmup W`,
 computed the way bench.py computes roofline.kernel_ms from HIP events: the union of the timed
 dispatches' [start, end] spans divided by K.  Also the mean duration of the serial frames rendered
 after the timed region (roofline.kernel_ms_serial).
 
-Frame order in bench.py (a frame: its non-stats path_persistent dispatch and its second pass's
+Frame order in bench.py --full (a frame: its non-stats path_persistent dispatch and its second pass's
 dispatches): S clock-settle frames (the bench line's config.settle_frames), W warmup, K timed, 3
 serial, then (one GPU) 2 drt_render frames.
 

@@ -8,7 +8,7 @@
 # Steps:
 #   tests[:EXPR]          pytest -m gpu over tests/ (-k EXPR if given)        -> gpurun_out/gpu_tests.log
 #   smoke                 __graft_entry__.smoke()                              -> gpurun_out/smoke.log
-#   bench[:ARGS]          python bench.py ARGS (default: the headline, 10 steps)  -> gpurun_out/bench.json
+#   bench[:ARGS]          python bench.py --full ARGS (default: the headline, 10 steps)  -> $OUT/bench.json
 #   prof[:ARGS]           rocprofv3 --kernel-trace --stats of bench.py ARGS + tools/rocprof_union.py
 #   mr:N                  tools/multirank_check.sh with N gloo ranks on the one GPU  -> gpurun_out/mrN.json
 #   matrix:REPS:S1;S2;..  tools/lib_matrix.sh REPS S1 S2 ... (S = "label|ENV=..|bench args")
@@ -41,12 +41,12 @@ for step in "$@"; do
       timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1
       rc=$?; tail -2 $OUT/smoke.log ;;
     bench)
-      timeout -k 10 600 python bench.py ${arg:---steps 10 --warmup 2} > $OUT/bench.json 2> $OUT/bench.err
+      timeout -k 10 600 python bench.py --full ${arg:---steps 10 --warmup 2} > $OUT/bench.json 2> $OUT/bench.err
       rc=$?; cut -c1-400 $OUT/bench.json; tail -2 $OUT/bench.err ;;
     prof)
       a=${arg:---steps 10 --warmup 2}
       timeout -k 10 600 rocprofv3 --kernel-trace --stats -d $OUT/prof -o run --output-format csv -- \
-        python3 bench.py $a --no-cpu-baseline > $OUT/prof_bench.json 2> $OUT/prof.err
+        python3 bench.py --full $a --no-cpu-baseline > $OUT/prof_bench.json 2> $OUT/prof.err
       rc=$?
       if [ $rc -eq 0 ]; then
         st=$(echo "$a" | sed -n 's/.*--steps \([0-9]*\).*/\1/p'); wu=$(echo "$a" | sed -n 's/.*--warmup \([0-9]*\).*/\1/p')

@@ -11,7 +11,7 @@ rc=$?; echo "shadow-tree pytest rc=$rc"; tail -12 $OUT/shadow_tree_tests.log
 if [ $rc -ge 2 ]; then exit $rc; fi
 ab() {  # label, env, bench args...
   local label=$1 v=$2; shift 2
-  env $v timeout -k 10 300 python bench.py --steps ${STEPS:-5} --warmup 1 --no-cpu-baseline --no-load-timing "$@" > $OUT/ab.json 2> $OUT/ab.err
+  env $v timeout -k 10 300 python bench.py --full --steps ${STEPS:-5} --warmup 1 --no-cpu-baseline --no-load-timing "$@" > $OUT/ab.json 2> $OUT/ab.err
   local rc=$?
   python - "$label" "$v" $OUT/ab.json >> $OUT/wide_ab.jsonl <<'PY'
 import json, sys
