@@ -18,7 +18,7 @@ from pathlib import Path
 import numpy as np
 
 from . import _lib
-from ._lib import ACCEL, FRAME_REFERENCE_ORDER, FRAME_STATS, DrtCamera, DrtFrameParams, DrtFrameStats, DrtOptions, DrtSceneInfo, check
+from ._lib import ACCEL, FRAME_REFERENCE_ORDER, FRAME_STATS, TRACE_GRID_TREE, DrtCamera, DrtFrameParams, DrtFrameStats, DrtOptions, DrtSceneInfo, check
 
 __all__ = ["Scene", "Renderer", "RendererGroup", "ACCEL", "load_skybox_dir", "SKY_FACES", "build"]
 
@@ -399,10 +399,12 @@ class Renderer:
         check(_lib.load().drt_trace_device(self.h, int(bool(shadow)), v(d_rays), int(n), v(d_t), v(d_normal),
                                            v(d_object), v(d_occluded), v(stream or 0)), self.h, "drt_trace_device")
 
-    def set_trace_stats(self, on=True, reference_order=False):
+    def set_trace_stats(self, on=True, reference_order=False, grid_tree=False):
         """Count traversal work (rays, nodes, leaves, primitives) of later batched queries;
-        reference_order: later shadow queries walk the reference's binary tree."""
-        flags = (FRAME_STATS if on else 0) | (FRAME_REFERENCE_ORDER if reference_order else 0)
+        reference_order: later shadow queries walk the reference's binary tree; grid_tree: a Grid
+        scene's later shadow queries run on its cell tree (DRT_TRACE_GRID_TREE), the answers unchanged."""
+        flags = (FRAME_STATS if on else 0) | (FRAME_REFERENCE_ORDER if reference_order else 0) | (
+            TRACE_GRID_TREE if grid_tree else 0)
         check(_lib.load().drt_set_trace_flags(self.h, flags), self.h, "drt_set_trace_flags")
 
     def trace_stats(self):

@@ -21,6 +21,7 @@ STATUS = {0: "DRT_OK", -1: "DRT_E_INVALID", -2: "DRT_E_HIP", -3: "DRT_E_NODEVICE
 ACCEL = {"none": 0, "grid": 1, "bvh": 2}
 FRAME_STATS = 1
 FRAME_REFERENCE_ORDER = 4  # shadow queries on the reference's binary tree, in its visit order
+TRACE_GRID_TREE = 8  # drt_set_trace_flags: a Grid scene's batched shadow queries on its cell tree
 
 _f = C.POINTER(C.c_float)
 _u8 = C.POINTER(C.c_uint8)

@@ -29,6 +29,8 @@ void launch_grid_stream(const SceneArgs& S, const TraceArgs& A, bool tri_only, b
                         hipStream_t st);
 void launch_grid_tree_stream(const SceneArgs& ST_, const SceneArgs& SG, const TraceArgs& A, bool stats, int waves,
                              int walk, int pairs, unsigned int* fb_counter, hipStream_t st);
+void launch_cell_tree_stream(const SceneArgs& S, const TraceArgs& A, bool tri_only, bool stats, int waves, hipStream_t st);
+void launch_cell_prep(const float* rays, int n, float4* out, hipStream_t st);
 void launch_wf_combine(const SceneArgs& S, const FrameArgs& F, const WfArgs& W, hipStream_t st);
 void launch_wf_combine_reduce(const SceneArgs& S, const FrameArgs& F, const WfArgs& W, const ReduceArgs& R,
                               hipStream_t st);
@@ -132,6 +134,12 @@ struct drt_ctx {
   bool has_gv = false;
   DevBuf d_gv_wnodes, d_gv_range, d_gv_prims, d_gv_big;
   uint32_t gv_wroot = 0;
+  // the Grid scene's cell tree (drt_upload_grid_shadow_bvh; drt_layout.hpp CellNodeRecord): 4-ary records of
+  // integer cell boxes, the listed primitives in its order with their cell range in q1.w / q2.w, its
+  // big-leaf table; ct_root: the root's descriptor
+  bool has_ct = false;
+  DevBuf d_ct_nodes, d_ct_prims, d_ct_big;
+  uint32_t ct_root = 0;
   // frame scratch
   DevBuf d_frame, d_rays, d_out, d_counter;
   // frame scratch per slot (drt_frame_params.slot): frames on different slots may be in flight
@@ -152,6 +160,7 @@ struct drt_ctx {
   bool stats_valid = false;  // the last frame ran with DRT_FRAME_STATS
   // batched queries: streaming-query records, primitive results, timing of the last call
   DevBuf d_tq, d_tprim, d_tstats;
+  DevBuf d_tfb;  // DRT_TRACE_GRID_TREE: the cell tree's undecided queries (TraceArgs::fb_rays)
   // tev: streaming-kernel start / end, query done.  Batched queries on one context share these
   // buffers and the claim counter, so each query waits for the previous one (tev[2]) on its own
   // stream, and a buffer is only regrown once that query has finished.
@@ -401,6 +410,167 @@ static bool build_wide(const drt_bvh_node* nodes, const std::vector<uint32_t>& l
   return true;
 }
 
+// DRT_GRID_CELL_TREE: 0 no cell tree, 1 for scenes with non-triangle primitives, 2 for triangle scenes too
+constexpr int kCellTreeDefault = DRT_GRID_CELL_TREE_DEFAULT;
+
+// The Grid's margin to a cell face, in cells (SceneArgs::gmargin): 128 eps K n_max, eps = 2^-23
+static double grid_margin(const drt_ctx* c) {
+  double K = 1.0;
+  int nm = 1;
+  for (int a = 0; a < 3; a++) {
+    const double w = (double)c->gmax[a] - (double)c->gmin[a];
+    K = std::max(K, 1.0 + (std::fabs((double)c->gmin[a]) + std::fabs((double)c->gmax[a])) / w);
+    nm = std::max(nm, c->gdim[a]);
+  }
+  return 128.0 * std::ldexp(1.0, -23) * K * nm;
+}
+
+// The Grid scene's cell tree (drt_cell_tree.hip): a 4-ary tree whose topology is the BVH's (nodes, order),
+// collapsed as build_wide collapses it, over the objects the Grid lists in some cell; each object's box is
+// its cell range (c->grid_cells), inner boxes are unions.  DRT_E_UNSUPPORTED: no tree for this scene.
+static int build_cell_tree(drt_ctx* c, const drt_bvh_node* nodes, uint32_t n_nodes, const uint32_t* order) {
+  for (int a = 0; a < 3; a++)
+    if (c->gdim[a] > kCellMaxDim) DRT_FAIL(c, DRT_E_UNSUPPORTED, "no cell tree: a grid axis over %d cells", kCellMaxDim);
+  if (!(grid_margin(c) < 0.25)) DRT_FAIL(c, DRT_E_UNSUPPORTED, "no cell tree: the grid's coordinates are too coarse");
+  auto listed_obj = [&](uint32_t k) { return c->grid_cells[(size_t)order[k] * 6 + 3] >= 0; };
+  // listed objects below each node (children follow their parent)
+  std::vector<uint32_t> listed(n_nodes, 0u);
+  for (uint32_t i = n_nodes; i-- > 0;) {
+    const drt_bvh_node& nd = nodes[i];
+    if (nd.leaf) {
+      for (uint32_t k = 0; k < nd.n_objs; k++) listed[i] += listed_obj(nd.index + k) ? 1u : 0u;
+    } else {
+      listed[i] = listed[nd.index] + listed[nd.index + 1];
+    }
+  }
+  if (!listed[0]) DRT_FAIL(c, DRT_E_UNSUPPORTED, "no cell tree: no object is listed in a cell");
+  auto skip = [&](uint32_t i) {  // through the nodes with one non-empty child
+    while (!nodes[i].leaf) {
+      const uint32_t l = nodes[i].index;
+      if (listed[l] && listed[l + 1]) break;
+      i = listed[l] ? l : l + 1;
+    }
+    return i;
+  };
+  auto area = [&](uint32_t i) {
+    const drt_bvh_node& nd = nodes[i];
+    const double x = (double)nd.bmax[0] - nd.bmin[0], y = (double)nd.bmax[1] - nd.bmin[1],
+                 z = (double)nd.bmax[2] - nd.bmin[2];
+    return x * y + y * z + z * x;
+  };
+  struct Box {
+    int lo[3] = {INT32_MAX, INT32_MAX, INT32_MAX}, hi[3] = {-1, -1, -1};
+    void add(const int32_t* r) {
+      for (int a = 0; a < 3; a++) {
+        lo[a] = std::min(lo[a], (int)r[a]);
+        hi[a] = std::max(hi[a], (int)r[3 + a]);
+      }
+    }
+  };
+  std::vector<PrimRecord> perm;
+  std::vector<uint2> big;
+  auto emit_leaf = [&](uint32_t i, Box& b) {  // the leaf's listed objects, each with its cell range
+    const drt_bvh_node& nd = nodes[i];
+    const uint32_t first = (uint32_t)perm.size();
+    for (uint32_t k = 0; k < nd.n_objs; k++) {
+      if (!listed_obj(nd.index + k)) continue;
+      const int32_t* r = &c->grid_cells[(size_t)order[nd.index + k] * 6];
+      PrimRecord p = c->prims_scene[order[nd.index + k]];
+      p.q[7] = bits_as_float(cell_pack(r[0], r[1], r[2]));
+      p.q[11] = bits_as_float(cell_pack(r[3], r[4], r[5]));
+      perm.push_back(p);
+      b.add(r);
+    }
+    if (listed[i] < kBigLeaf) return leaf_desc(first, listed[i]);
+    big.push_back(make_uint2(first, listed[i]));
+    return leaf_desc((uint32_t)big.size() - 1, kBigLeaf);
+  };
+  std::vector<CellNodeRecord> out;
+  std::vector<Box> cbox;  // per record and child
+  uint32_t root_desc;
+  const uint32_t r0 = skip(0);
+  int maxd = 0;
+  if (nodes[r0].leaf) {
+    Box b;
+    root_desc = emit_leaf(r0, b);
+  } else {
+    struct Item {
+      uint32_t node, rec;
+      int depth;
+    };
+    std::vector<Item> st{{r0, 0u, 1}};
+    out.emplace_back();
+    cbox.resize(4);
+    root_desc = 0;
+    while (!st.empty()) {
+      const Item it = st.back();
+      st.pop_back();
+      maxd = std::max(maxd, it.depth);
+      uint32_t ch[4];
+      int n = 2;
+      ch[0] = skip(nodes[it.node].index);
+      ch[1] = skip(nodes[it.node].index + 1);
+      while (n < 4) {  // the inner child with the largest box surface replaced by its two (build_wide)
+        int best = -1;
+        double ba = -1.0;
+        for (int k = 0; k < n; k++)
+          if (!nodes[ch[k]].leaf && area(ch[k]) > ba) {
+            ba = area(ch[k]);
+            best = k;
+          }
+        if (best < 0) break;
+        const uint32_t ci = ch[best];
+        ch[best] = skip(nodes[ci].index);
+        ch[n++] = skip(nodes[ci].index + 1);
+      }
+      std::stable_sort(ch, ch + n, [&](uint32_t a, uint32_t b) { return area(a) < area(b); });
+      CellNodeRecord r{};
+      for (int k = 0; k < 4; k++) r.desc[k] = kCellNoChild;
+      // children pushed in reverse so the first child's subtree follows its parent in memory
+      for (int k = n - 1; k >= 0; k--) {
+        if (nodes[ch[k]].leaf) {
+          r.desc[k] = emit_leaf(ch[k], cbox[4 * (size_t)it.rec + k]);
+        } else {
+          r.desc[k] = (uint32_t)out.size();
+          out.emplace_back();
+          cbox.resize(4 * out.size());
+          st.push_back({ch[k], r.desc[k], it.depth + 1});
+        }
+      }
+      out[it.rec] = r;
+    }
+    if (3 * maxd > kWideMaxStack) DRT_FAIL(c, DRT_E_UNSUPPORTED, "no cell tree: the tree is too deep");
+    // inner boxes bottom-up: a child record follows its parent
+    for (size_t i = out.size(); i-- > 0;)
+      for (int k = 0; k < 4; k++) {
+        const uint32_t d = out[i].desc[k];
+        if (d == kCellNoChild) continue;
+        Box& b = cbox[4 * i + k];
+        if (!desc_is_leaf(d))
+          for (int j = 0; j < 4; j++)
+            if (out[d].desc[j] != kCellNoChild) {
+              const Box& cb = cbox[4 * (size_t)d + j];
+              const int32_t r[6] = {cb.lo[0], cb.lo[1], cb.lo[2], cb.hi[0], cb.hi[1], cb.hi[2]};
+              b.add(r);
+            }
+        out[i].box[2 * k] = cell_pack(b.lo[0], b.lo[1], b.lo[2]);
+        out[i].box[2 * k + 1] = cell_pack(b.hi[0], b.hi[1], b.hi[2]);
+      }
+  }
+  if (out.empty()) out.emplace_back();
+  DRT_HIP(c, hipSetDevice(c->device));
+  DRT_HIP(c, c->d_ct_nodes.ensure(sizeof(CellNodeRecord) * out.size()));
+  DRT_HIP(c, hipMemcpy(c->d_ct_nodes.p, out.data(), sizeof(CellNodeRecord) * out.size(), hipMemcpyHostToDevice));
+  DRT_HIP(c, c->d_ct_prims.ensure(sizeof(PrimRecord) * perm.size() + kPrimPadBytes));
+  DRT_HIP(c, hipMemset(c->d_ct_prims.p, 0, sizeof(PrimRecord) * perm.size() + kPrimPadBytes));
+  DRT_HIP(c, hipMemcpy(c->d_ct_prims.p, perm.data(), sizeof(PrimRecord) * perm.size(), hipMemcpyHostToDevice));
+  DRT_HIP(c, c->d_ct_big.ensure(sizeof(uint2) * std::max<size_t>(1, big.size())));
+  if (!big.empty()) DRT_HIP(c, hipMemcpy(c->d_ct_big.p, big.data(), sizeof(uint2) * big.size(), hipMemcpyHostToDevice));
+  c->ct_root = root_desc;
+  c->has_ct = true;
+  return DRT_OK;
+}
+
 extern "C" {
 
 int drt_abi_version(void) { return DRT_ABI_VERSION; }
@@ -475,7 +645,7 @@ int drt_upload_scene(drt_ctx* c, const drt_scene_desc* s) {
   if (!c || !s) return DRT_E_INVALID;
   // Nothing renders against a half-replaced scene: the context's scene and accelerator are
   // invalid from here until this upload has committed every buffer.
-  c->has_scene = c->has_bvh = c->has_grid = c->has_gv = false;
+  c->has_scene = c->has_bvh = c->has_grid = c->has_gv = c->has_ct = false;
   if (s->camera.res_x <= 0 || s->camera.res_y <= 0) DRT_FAIL(c, DRT_E_INVALID, "camera resolution must be positive");
   if (s->n_prims < 0 || (s->n_prims > 0 && !s->prims)) DRT_FAIL(c, DRT_E_INVALID, "bad primitive array");
   if (s->n_lights < 0 || (s->n_lights > 0 && !s->lights)) DRT_FAIL(c, DRT_E_INVALID, "bad light array");
@@ -556,7 +726,7 @@ int drt_set_camera(drt_ctx* c, const drt_camera* k) {
 int drt_upload_bvh(drt_ctx* c, const drt_bvh_node* nodes, uint32_t n_nodes, const uint32_t* order, uint32_t n_obj) {
   if (!c || !nodes || n_nodes == 0) return DRT_E_INVALID;
   if (!c->has_scene) DRT_FAIL(c, DRT_E_STATE, "upload the scene before its BVH");
-  c->has_bvh = c->has_grid = c->has_gv = false;  // until this upload commits
+  c->has_bvh = c->has_grid = c->has_gv = c->has_ct = false;  // until this upload commits
   if ((int)n_obj != c->n_prims || (n_obj && !order)) DRT_FAIL(c, DRT_E_INVALID, "object_order must cover all %d objects", c->n_prims);
   std::vector<uint8_t> seen(n_obj, 0);
   for (uint32_t i = 0; i < n_obj; i++) {
@@ -732,7 +902,7 @@ int drt_upload_grid(drt_ctx* c, const int32_t dims[3], const float bmin[3], cons
                     const int32_t* co, int64_t n_refs) {
   if (!c || !dims || !bmin || !bmax || !cs || (n_refs > 0 && !co)) return DRT_E_INVALID;
   if (!c->has_scene) DRT_FAIL(c, DRT_E_STATE, "upload the scene before its grid");
-  c->has_bvh = c->has_grid = c->has_gv = false;  // until this upload commits
+  c->has_bvh = c->has_grid = c->has_gv = c->has_ct = false;  // until this upload commits
   // A scene without objects: Grid::Build's widths overflow (float FLT_MAX - -FLT_MAX), the cell
   // counts come out NaN -> INT_MIN and the grid has no cells (grid.cpp:56-67); its box is
   // inverted, so every ray misses it.  Same here with one empty cell under that box.
@@ -913,9 +1083,10 @@ int drt_upload_grid_shadow_bvh(drt_ctx* c, const drt_bvh_node* nodes, uint32_t n
                                uint32_t n_obj) {
   if (!c || !nodes || n_nodes == 0) return DRT_E_INVALID;
   if (!c->has_grid) DRT_FAIL(c, DRT_E_STATE, "upload the grid before its shadow tree");
-  c->has_gv = false;  // until this upload commits
+  c->has_gv = c->has_ct = false;  // until this upload commits
   if ((int)n_obj != c->n_prims || (n_obj && !order)) DRT_FAIL(c, DRT_E_INVALID, "object_order must cover all %d objects", c->n_prims);
-  if (!c->tri_only) DRT_FAIL(c, DRT_E_UNSUPPORTED, "the Grid's shadow tree serves triangle scenes");
+  const int cell = env_int("DRT_GRID_CELL_TREE", kCellTreeDefault);
+  if (!c->tri_only && cell < 1) DRT_FAIL(c, DRT_E_UNSUPPORTED, "the Grid's shadow tree serves triangle scenes (DRT_GRID_CELL_TREE=0)");
   if (n_obj > kFirstMask) DRT_FAIL(c, DRT_E_UNSUPPORTED, "more than %u objects", kFirstMask);
   std::vector<uint8_t> seen(n_obj, 0);
   for (uint32_t i = 0; i < n_obj; i++) {
@@ -928,6 +1099,11 @@ int drt_upload_grid_shadow_bvh(drt_ctx* c, const drt_bvh_node* nodes, uint32_t n
       DRT_FAIL(c, DRT_E_INVALID, "node %u out of range", i);
   }
   if (!wide_tree_valid(nodes, n_nodes, n_obj)) DRT_FAIL(c, DRT_E_INVALID, "not a tree of nested boxes over every object");
+  // the cell tree: scenes with other primitives than triangles, triangle scenes with DRT_GRID_CELL_TREE=2
+  if (!c->tri_only || cell >= 2) {
+    const int rc = build_cell_tree(c, nodes, n_nodes, order);
+    if (!c->tri_only || (rc && rc != DRT_E_UNSUPPORTED)) return rc;
+  }
   // leaf descriptors (oversized leaves through the big-leaf table, as drt_upload_bvh)
   std::vector<uint2> big;
   std::vector<uint32_t> dsc(n_nodes, 0u);
@@ -1023,15 +1199,8 @@ static int scene_args(drt_ctx* c, int accel, SceneArgs& S, bool reference_order)
     memcpy(S.gmin, c->gmin, sizeof(S.gmin));
     memcpy(S.gmax, c->gmax, sizeof(S.gmax));
     // the shadow tree's cell certificate (grid_certificate): n / width per axis, and 128 eps K n_max
-    double K = 1.0;
-    int nm = 1;
-    for (int a = 0; a < 3; a++) {
-      const double w = (double)c->gmax[a] - (double)c->gmin[a];
-      S.gscale[a] = (float)((double)c->gdim[a] / w);
-      K = std::max(K, 1.0 + (std::fabs((double)c->gmin[a]) + std::fabs((double)c->gmax[a])) / w);
-      nm = std::max(nm, c->gdim[a]);
-    }
-    const double margin = 128.0 * std::ldexp(1.0, -23) * K * nm;
+    for (int a = 0; a < 3; a++) S.gscale[a] = (float)((double)c->gdim[a] / ((double)c->gmax[a] - (double)c->gmin[a]));
+    const double margin = grid_margin(c);
     S.gmargin = margin < 0.25 ? (float)margin : 1.0f;  // (1: no certificate, every hit to the Grid walk)
     S.cell_start = c->d_cell_start.as<uint32_t>();
     S.gmacro = c->d_macro.as<uint32_t>();
@@ -1273,7 +1442,9 @@ static int plan_frame(drt_ctx* c, const drt_frame_params* p, Plan& P) {
     // (round 6, ADVICE r5: many lights x light_spp made a fixed 2^24-slot chunk ask for ~160 GB), whole
     // pixels (a multiple of nsub, so that wf_combine can fold the reduce)
     const uint64_t pairs = wf_pairs(c, F.light_spp);
-    const uint64_t slot_bytes = ((uint64_t)md + 1u) * (pairs * 41u + 16u);
+    // (+ 32 B per query of a Grid scene with a shadow tree: the undecided queries' list, TraceArgs::fb_rays)
+    const uint64_t qbytes = c->accel == DRT_ACCEL_GRID && (c->has_gv || c->has_ct) ? 73u : 41u;
+    const uint64_t slot_bytes = ((uint64_t)md + 1u) * (pairs * qbytes + 16u);
     const uint64_t budget = env_u64("DRT_WAVEFRONT_CHUNK_BYTES", 24ull << 30);
     uint64_t chunk = std::min<uint64_t>(P.n_slots, env_u64("DRT_WAVEFRONT_CHUNK_SLOTS", 1ull << 24));
     chunk = std::min<uint64_t>(chunk, budget / std::max<uint64_t>(1, slot_bytes));
@@ -1466,7 +1637,7 @@ static int run_frame(drt_ctx* c, const drt_frame_params* p, float* d_out, bool f
           c->d_wf_occ_s[slot].fit(std::max<uint64_t>(q, 1)) == hipSuccess &&
           c->d_wf_lvl_s[slot].fit(sizeof(float4) * levels * P.wf_chunk) == hipSuccess &&
           (!compact || c->d_wf_cnt_s[slot].fit(cnt_bytes) == hipSuccess) &&
-          (!(compact && c->accel == DRT_ACCEL_GRID && c->has_gv) ||
+          (!(compact && c->accel == DRT_ACCEL_GRID && (c->has_gv || c->has_ct)) ||
            c->d_wf_fb_s[slot].fit(2 * sizeof(float4) * std::max<uint64_t>(q, 1)) == hipSuccess)) {
         wavefront = true;
         W.rays = c->d_wf_rays_s[slot].as<float4>();
@@ -1589,7 +1760,26 @@ static int run_frame(drt_ctx* c, const drt_frame_params* p, float* d_out, bool f
         // counters stay the reference's cell / object counts (DRT_GRID_SHADOW_TREE=2: the tree there too,
         // its work in the wide_* counters); DRT_GRID_SHADOW_TREE=0: the walk for every frame.
         const int gv = env_int("DRT_GRID_SHADOW_TREE", 1);
-        if (c->has_gv && c->tri_only && c->d_wf_fb_s[slot].p && (gv >= 2 || (gv == 1 && !stats))) {
+        const bool tree = c->d_wf_fb_s[slot].p && (gv >= 2 || (gv == 1 && !stats));
+        if (tree && c->has_ct && env_int("DRT_GRID_CELL_TREE", kCellTreeDefault) >= (c->tri_only ? 2 : 1)) {
+          // the cell tree (drt_cell_tree.hip): scenes of any primitives; the undecided queries on grid_stream
+          SceneArgs SC = S;
+          SC.prims = c->d_ct_prims.as<float4>();
+          SC.wnodes = c->d_ct_nodes.as<float4>();
+          SC.wroot = c->ct_root;
+          SC.big_leaves = c->d_ct_big.as<uint2>();
+          A.refill_min = env_int("DRT_GRID_TREE_REFILL_MIN", 16);
+          A.fb_rays = c->d_wf_fb_s[slot].as<float4>();
+          A.fb_count = counter + 224;  // (zeroed with the chunk's claim counters)
+          launch_cell_tree_stream(SC, A, c->tri_only, stats, env_int("DRT_WAVEFRONT_WAVES", 7), st);
+          DRT_HIP(c, hipGetLastError());
+          TraceArgs B = A;  // the list's own claim counter, one partition (launch_grid_tree_stream)
+          B.counter = counter + 240;
+          B.parts = 1;
+          B.part_len = A.n;
+          B.refill_min = 16;
+          launch_grid_stream(S, B, c->tri_only, false, 7, F2.grid_walk, F2.grid_pairs, st);
+        } else if (tree && c->has_gv && c->tri_only) {
           SceneArgs ST = S;
           ST.prims = c->d_gv_prims.as<float4>();
           ST.wnodes = c->d_gv_wnodes.as<float4>();
@@ -1904,7 +2094,10 @@ static int trace_device(drt_ctx* c, const float* d_rays, int32_t n, int shadow, 
   DRT_HIP(c, hipSetDevice(c->device));
   c->trace_timed = false;
   c->trace_stats_valid = false;
-  if (c->accel != DRT_ACCEL_BVH) {
+  // DRT_TRACE_GRID_TREE: a Grid scene's shadow queries on its cell tree, the undecided ones on grid_stream
+  const bool cell = c->accel == DRT_ACCEL_GRID && shadow && (c->trace_flags & DRT_TRACE_GRID_TREE) && c->has_ct &&
+                    env_int("DRT_GRID_CELL_TREE", kCellTreeDefault) >= (c->tri_only ? 2 : 1);
+  if (c->accel != DRT_ACCEL_BVH && !cell) {
     launch_trace(S, c->accel, c->tri_only, d_rays, n, shadow, dt, dn, dobj, docc, st);
     DRT_HIP(c, hipGetLastError());
     return DRT_OK;
@@ -1920,6 +2113,46 @@ static int trace_device(drt_ctx* c, const float* d_rays, int32_t n, int shadow, 
   DRT_HIP(c, c->d_tstats.ensure(sizeof(unsigned long long) * ST_COUNT));
   const bool stats = (c->trace_flags & DRT_FRAME_STATS) != 0;
   float4* q = c->d_tq.as<float4>();
+  if (cell) {
+    if (c->trace_issued && c->d_tfb.bytes < 2 * sizeof(float4) * (size_t)n) DRT_HIP(c, hipEventSynchronize(c->tev[2]));
+    DRT_HIP(c, c->d_tfb.ensure(2 * sizeof(float4) * (size_t)n));
+    launch_cell_prep(d_rays, n, q, st);
+    DRT_HIP(c, hipMemsetAsync(c->d_counter.p, 0, 1024, st));
+    if (stats) DRT_HIP(c, hipMemsetAsync(c->d_tstats.p, 0, sizeof(unsigned long long) * ST_COUNT, st));
+    TraceArgs A{};
+    A.rays = q;
+    A.rays_b = q + 1;
+    A.stride = 2;
+    A.n = (uint32_t)n;
+    A.counter = c->d_counter.as<unsigned int>();
+    A.occ_out = docc;
+    A.stats = c->d_tstats.as<unsigned long long>();
+    A.refill_min = env_int("DRT_GRID_TREE_REFILL_MIN", 16);
+    A.parts = 1;
+    A.part_len = (uint32_t)n;
+    A.fb_rays = c->d_tfb.as<float4>();
+    A.fb_count = A.counter + 224;
+    SceneArgs SC = S;
+    SC.prims = c->d_ct_prims.as<float4>();
+    SC.wnodes = c->d_ct_nodes.as<float4>();
+    SC.wroot = c->ct_root;
+    SC.big_leaves = c->d_ct_big.as<uint2>();
+    DRT_HIP(c, hipEventRecord(c->tev[0], st));
+    launch_cell_tree_stream(SC, A, c->tri_only, stats, env_int("DRT_WAVEFRONT_WAVES", 7), st);
+    DRT_HIP(c, hipGetLastError());
+    TraceArgs B = A;  // the undecided queries' list: its own claim counter
+    B.counter = A.counter + 240;
+    B.refill_min = 16;
+    launch_grid_stream(S, B, c->tri_only, false, 7, std::max(0, env_int("DRT_REPLAY_GRID_WALK", 3)),
+                       std::max(1, env_int("DRT_REPLAY_GRID_PAIRS", 3)), st);
+    DRT_HIP(c, hipGetLastError());
+    DRT_HIP(c, hipEventRecord(c->tev[1], st));
+    DRT_HIP(c, hipEventRecord(c->tev[2], st));
+    c->trace_issued = true;
+    c->trace_timed = true;
+    c->trace_stats_valid = stats;
+    return DRT_OK;
+  }
   launch_trace_prep(d_rays, n, shadow, q, st);
   DRT_HIP(c, hipMemsetAsync(c->d_counter.p, 0, 256, st));
   if (stats) DRT_HIP(c, hipMemsetAsync(c->d_tstats.p, 0, sizeof(unsigned long long) * ST_COUNT, st));
@@ -2018,6 +2251,7 @@ int drt_trace_stats(drt_ctx* c, drt_frame_stats* out) {
       r.wide_leaf = s[ST_W_LEAF];
       r.wide_prims = s[ST_W_PRIMS];
       r.wide_verify = s[ST_W_VERIFY];
+      r.wide_grid_walks = s[ST_W_GRIDFB];
     }
   }
   *out = r;

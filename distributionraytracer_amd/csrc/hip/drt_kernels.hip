@@ -12,8 +12,7 @@
 #include <algorithm>
 #include <cstdlib>
 
-#include "drt_device.hpp"
-#include "drt_kernels.hpp"
+#include "drt_stream.hpp"
 
 namespace drt {
 
@@ -777,15 +776,7 @@ __global__ void __launch_bounds__(kBlock) path_kernel(SceneArgs S, FrameArgs F) 
 // work is left.  Results are per work item (sample) exactly as in path_kernel; the ordered
 // per-pixel reduce is unchanged, so frames are bit-identical.
 // ------------------------------------------------------------------------------------------
-constexpr uint32_t kNoItem = 0xFFFFFFFFu;
 constexpr uint32_t kPartYield = 0xFFFFFFFFu;  // MODE_SEQ tail: the wave hands its pixels over
-
-// LDS traversal-stack entries per thread for a given occupancy target (5 blocks of 256 threads
-// fit 16 entries in 160 KiB; 6-8 blocks need a shorter LDS stack, the rest spills to scratch).
-__host__ __device__ constexpr int lds_cap(int waves) {
-  // per thread: 160 KiB over waves * 4 SIMDs * 64 lanes, 8 B per entry, whatever the block size
-  return (160 * 1024 / (waves * 256 * 8) - 1) < 16 ? (160 * 1024 / (waves * 256 * 8) - 1) : 16;
-}
 
 // Per-lane state flags, packed into one VGPR: divergent bools kept as separate variables
 // become 64-bit SGPR lane masks that the loop has to carry (and spill) across iterations.
@@ -863,10 +854,6 @@ __device__ __forceinline__ bool box_test_finite(float mnx, float mny, float mnz,
   t = (in < 0.0f) ? 0.0f : te;
   return fmaxf(t0, 0.0f) < t1;
 }
-__device__ __forceinline__ bool ray_finite(const RayP& r) {
-  return inv_finite(r) && fabsf(r.o.x) < __builtin_inff() && fabsf(r.o.y) < __builtin_inff() &&
-         fabsf(r.o.z) < __builtin_inff();
-}
 // Shadow-tree lanes: finite rays; with the one-fma child test (DRT_WIDE_FMA1, node_step) also |inv| <=
 // 2^40 (no direction component below ~1e-12 of the ray's length) and |o| <= 2^60.
 __device__ __forceinline__ bool wide_ray_ok(const RayP& r) {
@@ -877,21 +864,6 @@ __device__ __forceinline__ bool wide_ray_ok(const RayP& r) {
   const float mo = fmaxf(fmaxf(fabsf(r.o.x), fabsf(r.o.y)), fabsf(r.o.z));
   return mi <= 0x1p40f && mo <= 0x1p60f;  // false for NaN
 #endif
-}
-
-// Grid::Traverse(Ray&)'s first step (grid.cpp:318-324): a shadow ray whose slab test misses the grid box
-// counts as shadowed.  The same float arithmetic as grid_traverse / grid_init.
-__device__ __forceinline__ bool grid_box_missed(const SceneArgs& S, const RayP& r) {
-  const float x0 = S.gmin[0], y0 = S.gmin[1], z0 = S.gmin[2], x1 = S.gmax[0], y1 = S.gmax[1], z1 = S.gmax[2];
-  float txmin, tymin, tzmin, txmax, tymax, tzmax;
-  if (r.sx()) { txmin = (x0 - r.o.x) * r.ix; txmax = (x1 - r.o.x) * r.ix; } else { txmin = (x1 - r.o.x) * r.ix; txmax = (x0 - r.o.x) * r.ix; }
-  if (r.sy()) { tymin = (y0 - r.o.y) * r.iy; tymax = (y1 - r.o.y) * r.iy; } else { tymin = (y1 - r.o.y) * r.iy; tymax = (y0 - r.o.y) * r.iy; }
-  if (r.sz()) { tzmin = (z0 - r.o.z) * r.iz; tzmax = (z1 - r.o.z) * r.iz; } else { tzmin = (z1 - r.o.z) * r.iz; tzmax = (z0 - r.o.z) * r.iz; }
-  float t0 = (txmin > tymin) ? txmin : tymin;
-  if (tzmin > t0) t0 = tzmin;
-  float t1 = (txmax < tymax) ? txmax : tymax;
-  if (tzmax < t1) t1 = tzmax;
-  return t0 > t1 || t1 < 0.0f;  // grid.cpp:170 (NaN compares false: not missed, as there)
 }
 
 // The Grid cell certificate of a shadow-tree hit (trace_stream GV).  Primitive P was hit at t < range.
@@ -2652,7 +2624,6 @@ __global__ void __launch_bounds__(pblock<ACC>(), WAVES) path_persistent(SceneArg
 // kernel runs at up to 8 waves per SIMD where the path kernel, which also carries shading
 // state, holds 6.  The node step is the path kernel's, specialised for one query kind.
 // ------------------------------------------------------------------------------------------
-constexpr uint32_t kTraceChunk = 256;  // queries claimed per wave per atomic
 // shadow-query records through the scalar cache when a wave's visiting lanes share one (node_step UNI;
 // -DDRT_UNI_FETCH, A/B): measured 2 418-2 447 against 2 487-2 495 Mrays/s on the headline and 3 284-3 356
 // against 3 421-3 442 on C3 (profiles/r05_ab_uniform_node_fetch.jsonl) — the lanes of a wave leave a

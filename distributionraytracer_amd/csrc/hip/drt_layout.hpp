@@ -102,6 +102,22 @@ struct LeafBoxRecord {
   float box[6];
   uint32_t pad[2];
 };
+// Cell tree (the Grid scene's shadow queries of any primitives, drt_cell_tree.hip): a 4-ary node of
+// boxes in integer cell coordinates, 48 B = the three 16-B slots an inner visit loads:
+//   s0 = (lo[0], hi[0], lo[1], hi[1])   s1 = (lo[2], hi[2], lo[3], hi[3])   s2 = desc[0..3]
+// lo / hi = x | y << 10 | z << 20, the child's first and last cell per axis (grid dimensions <= 1024);
+// an unused child has the descriptor kCellNoChild.  Its primitive records carry their own cell range in the
+// two words a shadow query does not read: q1.w = lo, q2.w = hi.
+struct CellNodeRecord {
+  uint32_t box[8];
+  uint32_t desc[4];
+};
+constexpr int kCellMaxDim = 1024;
+constexpr uint32_t kCellNoChild = 0xFFFFFFFFu;
+__host__ __device__ inline uint32_t cell_pack(int x, int y, int z) {
+  return (uint32_t)x | ((uint32_t)y << 10) | ((uint32_t)z << 20);
+}
+static_assert(sizeof(CellNodeRecord) == 48, "cell node record is 48 B");
 static_assert(sizeof(PrimRecord) == 48, "prim record is 48 B");
 static_assert(sizeof(NodeRecord) == 64, "node record is 64 B");
 static_assert(sizeof(WideNodeRecord4) == 64, "4-ary wide node record is 64 B");

@@ -12,7 +12,7 @@ struct drt_scene {
   Scene scene;
   BVH bvh;
   Grid grid;
-  // a triangle Grid scene's BVH for its shadow tree (drt_upload_grid_shadow_bvh; DRT_GRID_SHADOW_TREE=0: none)
+  // a Grid scene's BVH for its shadow tree (drt_upload_grid_shadow_bvh; DRT_GRID_SHADOW_TREE=0: none)
   BVH gv_bvh;
   bool has_gv_bvh = false;
   Material* current = nullptr;
@@ -145,14 +145,17 @@ int drt_scene_build(drt_scene* s) {  // main.cpp:1023-1049
   } else if (s->scene.GetAccelStruct() == GRID_ACC) {
     s->grid = Grid();  // Grid::Build appends to the grid's object list (grid.cpp:45)
     s->grid.Build(objs);
-    // the Grid frame's shadow queries walk a tree of the same objects (triangle scenes, round 6)
+    // the Grid frame's shadow queries walk a tree of the same objects (round 6: triangle scenes; the
+    // cell tree: scenes of any primitives)
     const char* e = getenv("DRT_GRID_SHADOW_TREE");
-    bool tri = !objs.empty() && !(e && atoi(e) == 0);
-    for (Object* o : objs)
-      if (!dynamic_cast<Triangle*>(o)) { tri = false; break; }
+    const char* ce = getenv("DRT_GRID_CELL_TREE");
+    bool want = true;  // a triangle scene; any primitives with the cell tree on (DRT_GRID_CELL_TREE >= 1)
+    if ((ce ? atoi(ce) : DRT_GRID_CELL_TREE_DEFAULT) < 1)
+      for (Object* o : objs)
+        if (!dynamic_cast<Triangle*>(o)) { want = false; break; }
     s->gv_bvh = BVH();
-    s->has_gv_bvh = tri;
-    if (tri) s->gv_bvh.Build(objs);
+    s->has_gv_bvh = !objs.empty() && !(e && atoi(e) == 0) && want;
+    if (s->has_gv_bvh) s->gv_bvh.Build(objs);
   } else {
     s->has_gv_bvh = false;
   }
@@ -244,9 +247,9 @@ int drt_scene_upload(drt_ctx* ctx, drt_scene* s) {
   const auto& ob = s->gv_bvh.objectOrder();
   std::vector<uint32_t> ord(ob.size());
   for (size_t i = 0; i < ob.size(); i++) ord[i] = (uint32_t)ob[i]->scene_index;
-  // without a tree the Grid walk answers every query: a tree the device cannot take is no error
-  const int g = drt_upload_grid_shadow_bvh(ctx, n.data(), (uint32_t)n.size(), ord.data(), (uint32_t)ord.size());
-  return g == DRT_E_UNSUPPORTED ? DRT_OK : g;
+  // without a tree the Grid walk answers every query: the optional tree failing, however, is no error
+  (void)drt_upload_grid_shadow_bvh(ctx, n.data(), (uint32_t)n.size(), ord.data(), (uint32_t)ord.size());
+  return rc;
 }
 
 int drt_group_scene_upload(drt_group* g, drt_scene* s) {

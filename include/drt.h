@@ -134,6 +134,11 @@ typedef struct {
  * hence every frame, is identical (an any-hit query does not depend on the visit order), and
  * drt_frame_stats counts that work in its wide_* fields. */
 enum { DRT_FRAME_STATS = 1, DRT_FRAME_SHARD_LAYOUT = 2, DRT_FRAME_REFERENCE_ORDER = 4 };
+/* drt_set_trace_flags only: a Grid scene's batched shadow queries (drt_trace_shadow, drt_trace_device) run
+ * on its cell tree (drt_upload_grid_shadow_bvh) with the Grid walk for the queries the tree leaves
+ * undecided; drt_trace_stats then reports the wide_* counters.  The answers are the walk's.  Without a cell
+ * tree the flag changes nothing. */
+enum { DRT_TRACE_GRID_TREE = 8 };
 
 typedef struct {
   uint32_t seed;       /* keyed-RNG seed                                                */
@@ -201,13 +206,23 @@ int drt_upload_bvh(drt_ctx* ctx, const drt_bvh_node* nodes, uint32_t n_nodes, co
                    uint32_t n_objects);
 int drt_upload_grid(drt_ctx* ctx, const int32_t dims[3], const float bmin[3], const float bmax[3],
                     const int64_t* cell_start /* nx*ny*nz+1 */, const int32_t* cell_objs, int64_t n_refs);
-/* Optional, after drt_upload_grid of a triangle scene (round 6): a BVH of the same objects (the
- * BVH::Build result, as drt_upload_bvh takes it).  The Grid frame's wavefront shadow queries then walk a
- * 4-ary tree collapsed from it with widened boxes, and a hit counts only with a Grid cell certificate
- * (the ray's point at the hit lies well inside a cell the object is listed in, so Grid::Traverse(Ray&),
- * grid.cpp:309-358, finds it too); queries without one are walked on the Grid.  The answers are
- * Grid::Traverse(Ray&)'s.  Any drt_upload_scene / drt_upload_grid / drt_upload_bvh drops it.
- * DRT_GRID_SHADOW_TREE=0 keeps the Grid walk for every query. */
+/* Optional, after drt_upload_grid: a BVH of the same objects (the BVH::Build result, as drt_upload_bvh
+ * takes it).  A triangle scene's wavefront shadow queries then walk a 4-ary tree collapsed from it with
+ * widened boxes, and a hit counts only with a Grid cell certificate (the ray's point at the hit lies well
+ * inside a cell the object is listed in, so Grid::Traverse(Ray&), grid.cpp:309-358, finds it too).
+ * A scene with other primitives (spheres, planes, boxes) gets a cell tree instead: the BVH's topology over
+ * the objects' cell ranges, in integer cell coordinates.  The walk tests an object exactly when the ray
+ * crosses its cell range, so a hit counts when the ray passes well inside that range and is ignored when
+ * the ray stays well outside it, whatever the primitive's own extent (a plane's reaches past its box).
+ * Queries neither tree decides are walked on the Grid, so the answers are Grid::Traverse(Ray&)'s.
+ * DRT_GRID_CELL_TREE: 0 (default) no cell tree (DRT_E_UNSUPPORTED for such a scene), 1 scenes with
+ * non-triangle primitives, 2 triangle scenes too, in place of the widened tree.  It is off by default
+ * because the shipped balls_high scene measured 0.46-0.50x the walk's frame rate on it
+ * (profiles/grid_cell_tree_ab.jsonl).  A grid with an axis over
+ * 1024 cells gets no cell tree (DRT_E_UNSUPPORTED; the walk answers).  Any drt_upload_scene /
+ * drt_upload_grid / drt_upload_bvh drops the trees.  DRT_GRID_SHADOW_TREE=0 keeps the Grid walk for every
+ * query. */
+#define DRT_GRID_CELL_TREE_DEFAULT 0
 int drt_upload_grid_shadow_bvh(drt_ctx* ctx, const drt_bvh_node* nodes, uint32_t n_nodes,
                                const uint32_t* object_order, uint32_t n_objects);
 
@@ -285,7 +300,8 @@ int drt_trace_shadow(drt_ctx* ctx, const float* rays, int32_t n, uint8_t* occlud
  * the device) for the previous one, whose scratch records and claim counter it reuses. */
 int drt_trace_device(drt_ctx* ctx, int shadow, const float* d_rays, int32_t n, float* d_t, float* d_normal,
                      int32_t* d_object, uint8_t* d_occluded, void* hip_stream);
-/* flags for later batched queries: DRT_FRAME_STATS counts their traversal work */
+/* flags for later batched queries: DRT_FRAME_STATS counts their traversal work, DRT_FRAME_REFERENCE_ORDER,
+ * DRT_TRACE_GRID_TREE */
 int drt_set_trace_flags(drt_ctx* ctx, int flags);
 /* Device time of the streaming traversal kernel of the most recent BVH batched query
  * (kernel_ms) and, with DRT_FRAME_STATS set, its ray / node / leaf / primitive counters;
