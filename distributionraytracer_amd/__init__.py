@@ -181,6 +181,18 @@ class Scene:
                                                order.ctypes.data_as(_lib._i32)), what="bvh_export")
         return dict(boxes=boxes, leaf=leaf, index=index, nobjs=nobj, order=order)
 
+    def set_bvh(self, boxes, leaf, index, nobjs, order):
+        """drt_scene_set_bvh, the inverse of bvh_export: install a tree (e.g. a device-built one) as the
+        scene's BVH; trace_cpu, bvh_export and info() then use it.  Refused (DRT_E_INVALID) unless it is
+        a well-formed tree over every object with nested boxes."""
+        b = _f32(boxes).reshape(-1, 6)
+        nodes = np.zeros(len(b), np.dtype([("box", np.float32, 6), ("leaf", np.uint32), ("index", np.uint32),
+                                           ("n_objs", np.uint32)]))
+        nodes["box"], nodes["leaf"], nodes["index"], nodes["n_objs"] = b, leaf, index, nobjs
+        o = np.ascontiguousarray(order, np.uint32)
+        check(_lib.load().drt_scene_set_bvh(self.h, nodes.ctypes.data, len(nodes), o.ctypes.data_as(_lib._u32),
+                                            len(o)), what="drt_scene_set_bvh")
+
     def trace_cpu(self, rays, shadow=False):
         """The scalar host path (BVH::Traverse / Grid::Traverse / the NONE scan on the CPU, one ray
         at a time): closest -> (t, normal, object); shadow -> occluded (uint8)."""
@@ -251,10 +263,26 @@ class Renderer:
         except Exception:
             pass
 
-    def upload(self, scene: Scene):
-        check(_lib.load().drt_scene_upload(self.h, scene.h), self.h, "drt_scene_upload")
+    def upload(self, scene: Scene, build="host"):
+        """build="host": the reference's binned-SAH tree, built on the CPU (drt_scene_build) if the scene
+        is not built yet.  build="device" (BVH scenes): a linear BVH built by HIP kernels from the
+        primitives on the device (drt_build_bvh_device) and installed in `scene` too — far quicker to
+        build, slower to trace (README.md, Use)."""
+        if build == "device":
+            check(_lib.load().drt_scene_upload_device_bvh(self.h, scene.h), self.h, "drt_scene_upload_device_bvh")
+        elif build == "host":
+            check(_lib.load().drt_scene_upload(self.h, scene.h), self.h, "drt_scene_upload")
+        else:
+            raise ValueError(f"build must be 'host' or 'device', not {build!r}")
         self.scene = scene
         return self
+
+    def bvh_build_info(self):
+        """drt_bvh_build_info of the last build="device" upload: nodes, leaves, depth and the build /
+        fetch / commit times in ms."""
+        i = _lib.DrtBvhBuildInfo()
+        check(_lib.load().drt_get_bvh_build_info(self.h, C.byref(i)), self.h, "drt_get_bvh_build_info")
+        return {n: (float(getattr(i, n)) if n.endswith("_ms") else int(getattr(i, n))) for n, _ in i._fields_}
 
     def set_camera(self, camera=None):
         """drt_set_camera: the uploaded scene's camera alone (the per-frame SetEye of the interactive
@@ -447,8 +475,16 @@ class RendererGroup:
             raise RuntimeError(f"{what} failed: {_lib.STATUS.get(rc, rc)} "
                                f"{_lib.load().drt_group_last_error(self.h).decode()}".strip())
 
-    def upload(self, scene: Scene):
-        self._check(_lib.load().drt_group_scene_upload(self.h, scene.h), "drt_group_scene_upload")
+    def upload(self, scene: Scene, build="host"):
+        """build="device": the tree is built once, on the first device (Renderer.upload), and the same
+        arrays are committed on every device."""
+        if build not in ("host", "device"):
+            raise ValueError(f"build must be 'host' or 'device', not {build!r}")
+        if build == "device":
+            self._check(_lib.load().drt_group_scene_upload_device_bvh(self.h, scene.h),
+                        "drt_group_scene_upload_device_bvh")
+        else:
+            self._check(_lib.load().drt_group_scene_upload(self.h, scene.h), "drt_group_scene_upload")
         self.scene = scene
         return self
 

@@ -100,6 +100,16 @@ class DrtSceneInfo(C.Structure):
                 ("bvh_nodes", C.c_int32), ("build_ms", C.c_double)]
 
 
+class DrtBvhNode(C.Structure):
+    _fields_ = [("bmin", C.c_float * 3), ("bmax", C.c_float * 3), ("leaf", C.c_uint32), ("index", C.c_uint32),
+                ("n_objs", C.c_uint32)]
+
+
+class DrtBvhBuildInfo(C.Structure):
+    _fields_ = [("n_nodes", C.c_uint32), ("n_leaves", C.c_uint32), ("depth", C.c_uint32), ("build_ms", C.c_double),
+                ("fetch_ms", C.c_double), ("commit_ms", C.c_double)]
+
+
 # Every symbol include/drt.h and include/drt_host.h declare, with its ctypes signature.
 SIGNATURES = {
     # drt.h
@@ -110,6 +120,8 @@ SIGNATURES = {
     "drt_upload_scene": (C.c_int, [_vp, C.POINTER(DrtSceneDesc)]),
     "drt_set_camera": (C.c_int, [_vp, C.POINTER(DrtCamera)]),
     "drt_upload_bvh": (C.c_int, [_vp, _vp, C.c_uint32, _u32, C.c_uint32]),
+    "drt_build_bvh_device": (C.c_int, [_vp, _vp, _u32, C.POINTER(DrtBvhBuildInfo)]),
+    "drt_get_bvh_build_info": (C.c_int, [_vp, C.POINTER(DrtBvhBuildInfo)]),
     "drt_upload_grid": (C.c_int, [_vp, _i32, _f, _f, _i64, _i32, C.c_int64]),
     "drt_upload_grid_shadow_bvh": (C.c_int, [_vp, _vp, C.c_uint32, _u32, C.c_uint32]),
     "drt_render": (C.c_int, [_vp, C.POINTER(DrtFrameParams), _f]),
@@ -141,6 +153,9 @@ SIGNATURES = {
     "drt_group_set_camera": (C.c_int, [_vp, C.POINTER(DrtCamera)]),
     # drt_host.h
     "drt_group_scene_upload": (C.c_int, [_vp, _vp]),
+    "drt_scene_set_bvh": (C.c_int, [_vp, _vp, C.c_uint32, _u32, C.c_uint32]),
+    "drt_scene_upload_device_bvh": (C.c_int, [_vp, _vp]),
+    "drt_group_scene_upload_device_bvh": (C.c_int, [_vp, _vp]),
     "drt_scene_new": (_vp, []),
     "drt_scene_load_p3f": (_vp, [C.c_char_p]),
     "drt_scene_free": (None, [_vp]),

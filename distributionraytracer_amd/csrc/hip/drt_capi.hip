@@ -2,6 +2,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <chrono>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -9,6 +10,7 @@
 #include <string>
 #include <vector>
 
+#include "drt_bvh_build.hpp"
 #include "drt_kernels.hpp"
 #include "drt_layout.hpp"
 
@@ -72,6 +74,24 @@ struct DevBuf {
   T* as() const { return (T*)p; }
 };
 
+struct PinnedBuf {  // grow-only pinned host staging (device -> host copies at copy-engine speed)
+  void* p = nullptr;
+  size_t bytes = 0;
+  ~PinnedBuf() {
+    if (p) (void)hipHostFree(p);
+  }
+  hipError_t ensure(size_t n) {
+    if (n <= bytes && p) return hipSuccess;
+    if (p) (void)hipHostFree(p);
+    p = nullptr;
+    bytes = 0;
+    hipError_t e = hipHostMalloc(&p, n ? n : 16, hipHostMallocDefault);
+    if (e == hipSuccess) bytes = n;
+    else p = nullptr;
+    return e;
+  }
+};
+
 }  // namespace
 
 struct drt_ctx {
@@ -97,6 +117,16 @@ struct drt_ctx {
   std::vector<drt_material> mats;
   DevBuf d_prims, d_lights, d_mats, d_sky[6];
   int has_sky = 0, sky_w[6] = {0}, sky_h[6] = {0}, sky_bpp[6] = {0};
+  // the device builder (drt_build_bvh_device): the scene-order drt_prim records (staged on the device by the
+  // first build after an upload), its scratch arena, its output (records, order, {nodes, leaves, depth}),
+  // pinned host copies of the output, events around the kernels and the fetch, the last build's figures
+  std::vector<drt_prim> prims_raw;
+  bool raw_resident = false;
+  DevBuf d_prims_raw, d_build, d_build_nodes, d_build_order, d_build_info;
+  PinnedBuf h_build_nodes, h_build_order, h_build_info;
+  hipEvent_t bev[3] = {nullptr, nullptr, nullptr};
+  drt_bvh_build_info build_info{};
+  bool has_build_info = false;
   // BVH
   bool has_bvh = false;
   DevBuf d_nodes, d_big;
@@ -627,6 +657,8 @@ void drt_destroy(drt_ctx* c) {
     if (e) (void)hipEventDestroy(e);
   for (auto& e : c->stage_ev)
     if (e) (void)hipEventDestroy(e);
+  for (auto& e : c->bev)
+    if (e) (void)hipEventDestroy(e);
   for (int k = 0; k < DRT_FRAME_SLOTS; k++) {
     if (c->aux[k]) {
       (void)hipStreamSynchronize(c->aux[k]);
@@ -703,6 +735,8 @@ int drt_upload_scene(drt_ctx* c, const drt_scene_desc* s) {
   c->mats = std::move(mats);
   c->n_prims = s->n_prims;
   c->prims_scene = std::move(prims);
+  c->prims_raw.assign(s->prims, s->prims + s->n_prims);
+  c->raw_resident = false;
   c->tri_only = tri_only;
   c->has_scene = true;
   return DRT_OK;
@@ -895,6 +929,74 @@ int drt_upload_bvh(drt_ctx* c, const drt_bvh_node* nodes, uint32_t n_nodes, cons
   DRT_HIP(c, hipMemcpy(c->d_prims.p, perm.data(), sizeof(PrimRecord) * perm.size(), hipMemcpyHostToDevice));
   c->has_bvh = true;
   c->has_grid = false;
+  return DRT_OK;
+}
+
+int drt_build_bvh_device(drt_ctx* c, drt_bvh_node* nodes_out, uint32_t* order_out, drt_bvh_build_info* info) {
+  if (!c) return DRT_E_INVALID;
+  if (!c->has_scene) DRT_FAIL(c, DRT_E_STATE, "upload the scene before building its BVH");
+  if (c->n_prims <= 0) DRT_FAIL(c, DRT_E_INVALID, "a scene without primitives has no BVH");
+  const uint32_t n = (uint32_t)c->n_prims;
+  if (n > kFirstMask) DRT_FAIL(c, DRT_E_UNSUPPORTED, "more than %u objects", kFirstMask);
+  c->has_bvh = c->has_grid = c->has_gv = c->has_ct = false;  // until the commit
+  DRT_HIP(c, hipSetDevice(c->device));
+  for (auto& e : c->bev)
+    if (!e) DRT_HIP(c, hipEventCreate(&e));
+  const size_t max_nodes = 2 * (size_t)n - 1;
+  DRT_HIP(c, c->d_prims_raw.ensure(sizeof(drt_prim) * n));
+  DRT_HIP(c, c->d_build.fit(bvh_build_scratch_bytes(n)));
+  DRT_HIP(c, c->d_build_nodes.fit(sizeof(drt_bvh_node) * max_nodes));
+  DRT_HIP(c, c->d_build_order.fit(sizeof(uint32_t) * n));
+  DRT_HIP(c, c->d_build_info.ensure(sizeof(uint32_t) * 4));
+  DRT_HIP(c, c->h_build_nodes.ensure(sizeof(drt_bvh_node) * max_nodes));
+  DRT_HIP(c, c->h_build_order.ensure(sizeof(uint32_t) * n));
+  DRT_HIP(c, c->h_build_info.ensure(sizeof(uint32_t) * 4));
+  hipStream_t st = c->stream;
+  DRT_HIP(c, hipEventRecord(c->bev[0], st));
+  if (!c->raw_resident) {
+    DRT_HIP(c, hipMemcpyAsync(c->d_prims_raw.p, c->prims_raw.data(), sizeof(drt_prim) * n, hipMemcpyHostToDevice, st));
+    c->raw_resident = true;
+  }
+  DRT_HIP(c, launch_bvh_build(c->d_prims_raw.as<drt_prim>(), n, c->d_build.p, c->d_build_nodes.as<drt_bvh_node>(),
+                              c->d_build_order.as<uint32_t>(), c->d_build_info.as<uint32_t>(), st));
+  DRT_HIP(c, hipEventRecord(c->bev[1], st));
+  uint32_t* hi = (uint32_t*)c->h_build_info.p;
+  DRT_HIP(c, hipMemcpyAsync(hi, c->d_build_info.p, sizeof(uint32_t) * 4, hipMemcpyDeviceToHost, st));
+  DRT_HIP(c, hipStreamSynchronize(st));
+  const uint32_t n_nodes = hi[0], n_leaves = hi[1], depth = hi[2];
+  if (n_nodes == 0 || n_nodes > max_nodes || n_nodes != 2 * n_leaves - 1)
+    DRT_FAIL(c, DRT_E_HIP, "the device build returned %u nodes, %u leaves for %u objects", n_nodes, n_leaves, n);
+  drt_bvh_node* hn = (drt_bvh_node*)c->h_build_nodes.p;
+  uint32_t* ho = (uint32_t*)c->h_build_order.p;
+  DRT_HIP(c, hipMemcpyAsync(hn, c->d_build_nodes.p, sizeof(drt_bvh_node) * n_nodes, hipMemcpyDeviceToHost, st));
+  DRT_HIP(c, hipMemcpyAsync(ho, c->d_build_order.p, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, st));
+  DRT_HIP(c, hipEventRecord(c->bev[2], st));
+  DRT_HIP(c, hipStreamSynchronize(st));
+  float build_ms = 0.f, fetch_ms = 0.f;
+  DRT_HIP(c, hipEventElapsedTime(&build_ms, c->bev[0], c->bev[1]));
+  DRT_HIP(c, hipEventElapsedTime(&fetch_ms, c->bev[1], c->bev[2]));
+  const auto t0 = std::chrono::steady_clock::now();
+  const int rc = drt_upload_bvh(c, hn, n_nodes, ho, n);
+  if (rc) return rc;
+  drt_bvh_build_info bi{};
+  bi.n_nodes = n_nodes;
+  bi.n_leaves = n_leaves;
+  bi.depth = depth;
+  bi.build_ms = build_ms;
+  bi.fetch_ms = fetch_ms;
+  bi.commit_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  c->build_info = bi;
+  c->has_build_info = true;
+  if (nodes_out) memcpy(nodes_out, hn, sizeof(drt_bvh_node) * n_nodes);
+  if (order_out) memcpy(order_out, ho, sizeof(uint32_t) * n);
+  if (info) *info = bi;
+  return DRT_OK;
+}
+
+int drt_get_bvh_build_info(const drt_ctx* c, drt_bvh_build_info* info) {
+  if (!c || !info) return DRT_E_INVALID;
+  if (!c->has_build_info) return DRT_E_STATE;
+  *info = c->build_info;
   return DRT_OK;
 }
 

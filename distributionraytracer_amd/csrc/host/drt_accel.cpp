@@ -211,6 +211,59 @@ void BVH::Build(std::vector<Object*>& objs) {  // bvh.cpp:27-44
   build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
 }
 
+int BVH::Set(const std::vector<Object*>& objs, const drt_bvh_node* nd, uint32_t n_nodes, const uint32_t* order,
+             uint32_t n_objects) {
+  if (!nd || n_nodes == 0 || n_objects != objs.size() || (n_objects && !order)) return DRT_E_INVALID;
+  std::vector<uint8_t> seen(n_objects, 0);
+  for (uint32_t i = 0; i < n_objects; i++) {
+    if (order[i] >= n_objects || seen[order[i]]) return DRT_E_INVALID;
+    seen[order[i]] = 1;
+  }
+  // one walk from the root: each node once, each position of object_order in one leaf, boxes nested
+  std::vector<uint8_t> node_seen(n_nodes, 0), pos_seen(n_objects, 0);
+  std::vector<std::pair<uint32_t, int>> st{{0u, 1}};
+  node_seen[0] = 1;
+  uint32_t reached = 0, covered = 0;
+  while (!st.empty()) {
+    const auto [i, d] = st.back();
+    st.pop_back();
+    reached++;
+    const drt_bvh_node& p = nd[i];
+    if (d >= 96) return DRT_E_INVALID;  // the traversal stack's bound (drt_upload_bvh refuses deeper trees)
+    if (p.leaf) {
+      if ((uint64_t)p.index + p.n_objs > n_objects) return DRT_E_INVALID;
+      for (uint32_t k = 0; k < p.n_objs; k++) {
+        if (pos_seen[p.index + k]) return DRT_E_INVALID;
+        pos_seen[p.index + k] = 1;
+      }
+      covered += p.n_objs;
+      continue;
+    }
+    if ((uint64_t)p.index + 1 >= n_nodes || p.index <= i) return DRT_E_INVALID;
+    for (uint32_t c = p.index; c <= p.index + 1; c++) {
+      if (node_seen[c]) return DRT_E_INVALID;
+      node_seen[c] = 1;
+      for (int a = 0; a < 3; a++)
+        if (!(nd[c].bmin[a] >= p.bmin[a] && nd[c].bmax[a] <= p.bmax[a])) return DRT_E_INVALID;
+      st.push_back({c, d + 1});
+    }
+  }
+  if (reached != n_nodes || covered != n_objects) return DRT_E_INVALID;
+  nodes.assign(n_nodes, Node());
+  for (uint32_t i = 0; i < n_nodes; i++) {
+    Node& o = nodes[i];
+    o.bbox = AABB(Vector(nd[i].bmin[0], nd[i].bmin[1], nd[i].bmin[2]), Vector(nd[i].bmax[0], nd[i].bmax[1], nd[i].bmax[2]));
+    o.leaf = nd[i].leaf != 0;
+    o.index = nd[i].index;
+    o.n_objs = o.leaf ? nd[i].n_objs : 0u;
+  }
+  objects.resize(n_objects);
+  for (uint32_t i = 0; i < n_objects; i++) objects[i] = objs[order[i]];
+  boxes_.clear(); cents_.clear(); order_.clear();
+  build_ms = 0.0;
+  return DRT_OK;
+}
+
 int BVH::upload(drt_ctx* ctx) const {
   std::vector<drt_bvh_node> nd(nodes.size());
   for (size_t i = 0; i < nodes.size(); i++) {

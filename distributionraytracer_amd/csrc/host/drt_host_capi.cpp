@@ -262,6 +262,70 @@ int drt_group_scene_upload(drt_group* g, drt_scene* s) {
   return DRT_OK;
 }
 
+int drt_scene_set_bvh(drt_scene* s, const drt_bvh_node* nodes, uint32_t n_nodes, const uint32_t* order,
+                      uint32_t n_objects) {
+  if (!s) return DRT_E_INVALID;
+  if (s->scene.GetAccelStruct() != BVH_ACC) return DRT_E_STATE;
+  const int rc = s->bvh.Set(s->scene.objectList(), nodes, n_nodes, order, n_objects);
+  if (rc) return rc;
+  s->has_gv_bvh = false;
+  s->built = true;
+  return DRT_OK;
+}
+
+// the scene description alone (upload_scene without its accelerator), then the tree from the device
+static int upload_for_device_build(drt_ctx* ctx, drt_scene* s) {
+  if (!ctx || !s) return DRT_E_INVALID;
+  if (!s->scene.GetCamera()) return DRT_E_STATE;
+  if (s->scene.GetSkyBoxFlg() && !s->scene.SkyboxComplete()) return DRT_E_STATE;
+  if (s->scene.GetAccelStruct() != BVH_ACC) return DRT_E_STATE;
+  drt_scene_desc d;
+  std::vector<drt_prim> prims;
+  std::vector<drt_light> ls;
+  std::vector<drt_material> ms;
+  s->scene.describe(d, prims, ls, ms);
+  return drt_upload_scene(ctx, &d);
+}
+
+int drt_scene_upload_device_bvh(drt_ctx* ctx, drt_scene* s) {
+  int rc = upload_for_device_build(ctx, s);
+  if (rc) return rc;
+  const size_t n = (size_t)s->scene.getNumObjects();
+  if (n == 0) return DRT_E_INVALID;
+  std::vector<drt_bvh_node> nodes(2 * n - 1);
+  std::vector<uint32_t> order(n);
+  drt_bvh_build_info info;
+  rc = drt_build_bvh_device(ctx, nodes.data(), order.data(), &info);
+  if (rc) return rc;
+  return drt_scene_set_bvh(s, nodes.data(), info.n_nodes, order.data(), (uint32_t)n);
+}
+
+int drt_group_scene_upload_device_bvh(drt_group* g, drt_scene* s) {
+  if (!g || !s) return DRT_E_INVALID;
+  int rc = drt_scene_upload_device_bvh(drt_group_ctx(g, 0), s);  // built once, on rank 0
+  if (rc) return rc;
+  const auto& nd = s->bvh.nodeList();
+  std::vector<drt_bvh_node> nodes(nd.size());
+  for (size_t i = 0; i < nd.size(); i++) {
+    const AABB& b = nd[i].bbox;
+    nodes[i].bmin[0] = b.min.x; nodes[i].bmin[1] = b.min.y; nodes[i].bmin[2] = b.min.z;
+    nodes[i].bmax[0] = b.max.x; nodes[i].bmax[1] = b.max.y; nodes[i].bmax[2] = b.max.z;
+    nodes[i].leaf = nd[i].leaf ? 1u : 0u;
+    nodes[i].index = nd[i].index;
+    nodes[i].n_objs = nd[i].leaf ? nd[i].n_objs : 0u;
+  }
+  const auto& ob = s->bvh.objectOrder();
+  std::vector<uint32_t> order(ob.size());
+  for (size_t i = 0; i < ob.size(); i++) order[i] = (uint32_t)ob[i]->scene_index;
+  for (int r = 1; r < drt_group_size(g); r++) {  // the same host arrays on every other rank
+    rc = upload_for_device_build(drt_group_ctx(g, r), s);
+    if (rc) return rc;
+    rc = drt_upload_bvh(drt_group_ctx(g, r), nodes.data(), (uint32_t)nodes.size(), order.data(), (uint32_t)order.size());
+    if (rc) return rc;
+  }
+  return DRT_OK;
+}
+
 int drt_scene_load_skybox(drt_scene* s, const char* dir) {
   if (!s || !dir) return DRT_E_INVALID;
   if (!s->scene.LoadSkybox(dir)) return DRT_E_INVALID;

@@ -204,6 +204,29 @@ int drt_upload_scene(drt_ctx* ctx, const drt_scene_desc* scene);
 int drt_set_camera(drt_ctx* ctx, const drt_camera* camera);
 int drt_upload_bvh(drt_ctx* ctx, const drt_bvh_node* nodes, uint32_t n_nodes, const uint32_t* object_order,
                    uint32_t n_objects);
+/* A second builder, on the device: a linear BVH (Karras 2012) of the resident primitives — Morton keys of
+ * the box centroids, a stable radix sort, the binary radix tree, a refit — in hand-written HIP
+ * (csrc/hip/drt_bvh_build.hip).  The tree is not the reference's binned-SAH tree (drt_scene_build keeps that
+ * one, node for node); it has the same shape rules (leaves of one or two objects, children side by side),
+ * every object's box is the host's GetBoundingBox() bit for bit, and it is committed through drt_upload_bvh
+ * itself, so closest hits and occlusion answers are the scene's.  The build is deterministic. */
+typedef struct {
+  uint32_t n_nodes, n_leaves, depth;
+  double build_ms;   /* device time of the build kernels, HIP events; the first build after a
+                        drt_upload_scene also stages the primitives' vertices on the device (the resident
+                        records hold triangle edges, which do not give the vertices back bit for bit),
+                        and that copy is inside this time                                             */
+  double fetch_ms;   /* device -> host copy of nodes and order                  */
+  double commit_ms;  /* host clock around the existing drt_upload_bvh commit    */
+} drt_bvh_build_info;
+
+/* After drt_upload_scene: build a BVH of the resident primitives on the device and commit it
+ * exactly as drt_upload_bvh would.  nodes_out (capacity 2*n_prims-1) / order_out (n_prims) may be
+ * NULL; otherwise they receive the tree.  DRT_E_STATE without a scene, DRT_E_INVALID for a scene without
+ * primitives, DRT_E_OOM / DRT_E_HIP as elsewhere. */
+int drt_build_bvh_device(drt_ctx* ctx, drt_bvh_node* nodes_out, uint32_t* order_out, drt_bvh_build_info* info);
+/* The figures of the context's last drt_build_bvh_device (DRT_E_STATE before one). */
+int drt_get_bvh_build_info(const drt_ctx* ctx, drt_bvh_build_info* info);
 int drt_upload_grid(drt_ctx* ctx, const int32_t dims[3], const float bmin[3], const float bmax[3],
                     const int64_t* cell_start /* nx*ny*nz+1 */, const int32_t* cell_objs, int64_t n_refs);
 /* Optional, after drt_upload_grid: a BVH of the same objects (the BVH::Build result, as drt_upload_bvh

@@ -81,6 +81,19 @@ int drt_scene_set_eye(drt_scene* s, const float eye[3]);
 int drt_scene_upload(drt_ctx* ctx, drt_scene* s);
 /* drt_scene_upload to every device of a group (include/drt.h, drt_group_*). */
 int drt_group_scene_upload(drt_group* g, drt_scene* s);
+/* Install a caller's tree as a BVH scene's BVH (the inverse of drt_scene_bvh_export): records and object
+ * order as drt_upload_bvh takes them.  Validated as there, and further: every node reached exactly once
+ * from the root, every object in exactly one leaf, every child box inside its parent's (DRT_E_INVALID
+ * otherwise, the scene unchanged; DRT_E_STATE for a scene whose accelerator is not the BVH).  Marks the
+ * scene built: drt_scene_trace_cpu, drt_scene_bvh_export, drt_scene_info and drt_scene_upload use it. */
+int drt_scene_set_bvh(drt_scene* s, const drt_bvh_node* nodes, uint32_t n_nodes, const uint32_t* object_order,
+                      uint32_t n_objects);
+/* drt_scene_upload of a BVH scene without the host build: the scene description, then
+ * drt_build_bvh_device (include/drt.h), whose tree is installed with drt_scene_set_bvh, so the host
+ * scene and the device walk the same tree.  The group form builds once, on rank 0, and commits the same
+ * host arrays on every rank with drt_upload_bvh. */
+int drt_scene_upload_device_bvh(drt_ctx* ctx, drt_scene* s);
+int drt_group_scene_upload_device_bvh(drt_group* g, drt_scene* s);
 /* The scene's current camera frame to a context / every device of a group (drt_set_camera): the
  * per-frame camera of the interactive renderer (main.cpp:530-533) with the scene resident. */
 int drt_scene_upload_camera(drt_ctx* ctx, const drt_scene* s);

@@ -355,6 +355,13 @@ class BVH {
   BVH() = default;
   int getNumObjects() const { return (int)objects.size(); }
   void Build(std::vector<Object*>& objs);  // bvh.cpp:27-227, tree-identical (threaded)
+  // A caller's tree over `objs` in place of Build's (drt_scene_set_bvh; e.g. the device-built LBVH of
+  // drt_build_bvh_device): records and object order as drt_upload_bvh takes them.  DRT_E_INVALID, and the
+  // tree left as it was, unless order is a permutation, every node is reached exactly once from the root
+  // with its children at index, index + 1 > its own index, the leaves cover object_order exactly once, the
+  // depth fits the traversal stack and every child box lies inside its parent's.
+  int Set(const std::vector<Object*>& objs, const drt_bvh_node* nd, uint32_t n_nodes, const uint32_t* order,
+          uint32_t n_objects);
   // Scalar queries on the CPU (bvh.cpp:231-314 closest, :316-391 shadow: normalises `ray`,
   // occluded if a hit lies within |d| + EPSILON)
   bool Traverse(Ray& ray, Object** hit_obj, HitRecord& hitRec) const;

@@ -1,0 +1,120 @@
+"""The two BVH builders on the headline scene (bench.py's 1M triangles plus floor, 512x512 at 64 spp):
+the host's binned-SAH build (drt_scene_build, tree-identical to the reference) against the device LBVH
+(drt_build_bvh_device), and the headline frame on either tree.
+
+Two JSON lines:
+  builds  --rounds interleaved rounds after one warm-up round, each on a fresh Scene: the host build's ms
+          (host clock around drt_scene_build) and the device build's three drt_bvh_build_info times (HIP
+          events around the kernels and around the fetch, host clock around the drt_upload_bvh commit), plus
+          the host clock around each whole upload call;
+  frames  two contexts in one process, one per tree, alternating frame by frame: device ms of the frame
+          (HIP events), Mrays/s = (closest + shadow traversals of a stats frame) / median ms, the
+          shadow-query stream's ms (drt_frame_stage_times) and the binary tree's depth.
+
+  python tools/bvh_build_ab.py [--rounds 10] [--tris 1000000] > profiles/gpu_bvh_build.jsonl
+"""
+import argparse
+import json
+import sys
+import time
+from pathlib import Path
+
+import numpy as np
+
+ROOT = Path(__file__).resolve().parents[1]
+sys.path.insert(0, str(ROOT))
+
+import bench  # noqa: E402
+import distributionraytracer_amd as drt  # noqa: E402
+
+
+def spread(a):
+    a = np.asarray(a, np.float64)
+    return {"median": round(float(np.median(a)), 3), "min": round(float(a.min()), 3), "max": round(float(a.max()), 3)}
+
+
+def tree_depth(tree):
+    """depth of an exported tree (root = 1), level by level"""
+    level, depth = np.zeros(1, np.int64), 0
+    while len(level):
+        depth += 1
+        inner = level[tree["leaf"][level] == 0]
+        left = tree["index"][inner].astype(np.int64)
+        level = np.concatenate([left, left + 1])
+    return depth
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rounds", type=int, default=10)
+    ap.add_argument("--tris", type=int, default=1_000_000)
+    ap.add_argument("--res", type=int, default=512)
+    ap.add_argument("--spp", type=int, default=64)
+    args = ap.parse_args()
+    tris = bench.synthetic_triangles(args.tris)
+
+    def fresh():
+        s = drt.Scene()
+        bench.populate(s, tris, args.res, args.spp)
+        return s
+
+    ctx = {"host": drt.Renderer(0), "device": drt.Renderer(0)}
+    rows = {"host_build_ms": [], "host_upload_wall_ms": [], "device_build_ms": [], "device_fetch_ms": [],
+            "device_commit_ms": [], "device_upload_wall_ms": []}
+    scenes = {}
+    for rnd in range(args.rounds + 1):  # round 0 warms both arms up (code objects, allocations, pinned buffers)
+        s = fresh()
+        t0 = time.perf_counter()
+        s.build()
+        t1 = time.perf_counter()
+        ctx["host"].upload(s)
+        t2 = time.perf_counter()
+        d = fresh()
+        t3 = time.perf_counter()
+        ctx["device"].upload(d, build="device")
+        t4 = time.perf_counter()
+        scenes = {"host": s, "device": d}
+        if rnd == 0:
+            continue
+        bi = ctx["device"].bvh_build_info()
+        rows["host_build_ms"].append((t1 - t0) * 1e3)
+        rows["host_upload_wall_ms"].append((t2 - t0) * 1e3)
+        rows["device_build_ms"].append(bi["build_ms"])
+        rows["device_fetch_ms"].append(bi["fetch_ms"])
+        rows["device_commit_ms"].append(bi["commit_ms"])
+        rows["device_upload_wall_ms"].append((t4 - t3) * 1e3)
+    out = {"record": "builds", "objects": int(scenes["host"].info().n_objects), "rounds": args.rounds}
+    out.update({k: spread(v) for k, v in rows.items()})
+    out["host_build_over_device_build_plus_fetch"] = round(
+        out["host_build_ms"]["median"] / (out["device_build_ms"]["median"] + out["device_fetch_ms"]["median"]), 1)
+    print(json.dumps(out), flush=True)
+
+    arms = ("host", "device")
+    rays, ms, stream = {}, {a: [] for a in arms}, {a: [] for a in arms}
+    for a in arms:
+        ctx[a].render(seed=7, stats=True)
+        st = ctx[a].stats()
+        rays[a] = st["closest_rays"] + st["shadow_rays"]
+    for rnd in range(args.rounds + 2):  # two warm-up rounds
+        for a in arms:
+            ctx[a].render(seed=7)
+            if rnd >= 2:
+                ms[a].append(float(ctx[a].frame_times(1)[1][-1]))
+                try:
+                    stream[a].append(float(ctx[a].frame_stage_times()["stream"]))
+                except RuntimeError:  # not a wavefront frame: no shadow-query stream to time
+                    stream[a].append(float("nan"))
+    out = {"record": "frames", "res": args.res, "spp": args.spp, "rounds": args.rounds}
+    for a in arms:
+        m = spread(ms[a])
+        out[a] = {"frame_ms": m, "mrays_s": round(rays[a] / m["median"] / 1e3, 1), "rays": int(rays[a]),
+                  "trace_stream_ms": spread(stream[a]), "bvh_depth": tree_depth(scenes[a].bvh_export()),
+                  "bvh_nodes": int(scenes[a].info().bvh_nodes)}
+    out["device_over_host_frame_rate"] = round(out["host"]["frame_ms"]["median"] / out["device"]["frame_ms"]["median"], 3)
+    print(json.dumps(out), flush=True)
+    for r in ctx.values():
+        r.close()
+
+
+if __name__ == "__main__":
+    main()
