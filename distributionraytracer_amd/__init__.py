@@ -263,19 +263,37 @@ class Renderer:
         except Exception:
             pass
 
-    def upload(self, scene: Scene, build="host"):
+    def upload(self, scene: Scene, build="host", commit="host", install=True):
         """build="host": the reference's binned-SAH tree, built on the CPU (drt_scene_build) if the scene
         is not built yet.  build="device" (BVH scenes): a linear BVH built by HIP kernels from the
         primitives on the device (drt_build_bvh_device) and installed in `scene` too — far quicker to
-        build, slower to trace (README.md, Use)."""
-        if build == "device":
-            check(_lib.load().drt_scene_upload_device_bvh(self.h, scene.h), self.h, "drt_scene_upload_device_bvh")
-        elif build == "host":
-            check(_lib.load().drt_scene_upload(self.h, scene.h), self.h, "drt_scene_upload")
-        else:
+        build, slower to trace (README.md, Use).  With build="device", commit="device" also lays out the
+        records and the shadow tree by HIP kernels (drt_build_bvh_device_commit; the same answers and
+        traversal counts), and install=False leaves `scene` without the tree: nothing but status words
+        comes back from the device, and scene.trace_cpu / scene.bvh_export behave as on an unbuilt scene."""
+        if build not in ("host", "device"):
             raise ValueError(f"build must be 'host' or 'device', not {build!r}")
+        if commit not in ("host", "device"):
+            raise ValueError(f"commit must be 'host' or 'device', not {commit!r}")
+        if build == "host" and (commit == "device" or not install):
+            raise ValueError("commit='device' and install=False need build='device'")
+        if build == "host":
+            check(_lib.load().drt_scene_upload(self.h, scene.h), self.h, "drt_scene_upload")
+        elif commit == "host" and install:
+            check(_lib.load().drt_scene_upload_device_bvh(self.h, scene.h), self.h, "drt_scene_upload_device_bvh")
+        else:
+            flags = (_lib.BVH_COMMIT_DEVICE if commit == "device" else 0) | (0 if install else _lib.BVH_NO_INSTALL)
+            check(_lib.load().drt_scene_upload_device_bvh_ex(self.h, scene.h, flags), self.h,
+                  "drt_scene_upload_device_bvh_ex")
         self.scene = scene
         return self
+
+    def bvh_commit_info(self):
+        """drt_bvh_commit_info of the resident BVH: on_device (1 after commit="device"), has_wide, n_slots
+        (64-B inner record slots, padding included), n_wide (4-ary shadow-tree records)."""
+        i = _lib.DrtBvhCommitInfo()
+        check(_lib.load().drt_get_bvh_commit_info(self.h, C.byref(i)), self.h, "drt_get_bvh_commit_info")
+        return {n: int(getattr(i, n)) for n, _ in i._fields_}
 
     def bvh_build_info(self):
         """drt_bvh_build_info of the last build="device" upload: nodes, leaves, depth and the build /

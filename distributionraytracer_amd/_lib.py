@@ -110,6 +110,12 @@ class DrtBvhBuildInfo(C.Structure):
                 ("fetch_ms", C.c_double), ("commit_ms", C.c_double)]
 
 
+class DrtBvhCommitInfo(C.Structure):
+    _fields_ = [("on_device", C.c_uint32), ("has_wide", C.c_uint32), ("n_slots", C.c_uint32), ("n_wide", C.c_uint32)]
+
+
+BVH_COMMIT_DEVICE, BVH_NO_INSTALL = 1, 2  # drt_scene_upload_device_bvh_ex flags (include/drt_host.h)
+
 # Every symbol include/drt.h and include/drt_host.h declare, with its ctypes signature.
 SIGNATURES = {
     # drt.h
@@ -122,6 +128,8 @@ SIGNATURES = {
     "drt_upload_bvh": (C.c_int, [_vp, _vp, C.c_uint32, _u32, C.c_uint32]),
     "drt_build_bvh_device": (C.c_int, [_vp, _vp, _u32, C.POINTER(DrtBvhBuildInfo)]),
     "drt_get_bvh_build_info": (C.c_int, [_vp, C.POINTER(DrtBvhBuildInfo)]),
+    "drt_build_bvh_device_commit": (C.c_int, [_vp, _vp, _u32, C.POINTER(DrtBvhBuildInfo)]),
+    "drt_get_bvh_commit_info": (C.c_int, [_vp, C.POINTER(DrtBvhCommitInfo)]),
     "drt_upload_grid": (C.c_int, [_vp, _i32, _f, _f, _i64, _i32, C.c_int64]),
     "drt_upload_grid_shadow_bvh": (C.c_int, [_vp, _vp, C.c_uint32, _u32, C.c_uint32]),
     "drt_render": (C.c_int, [_vp, C.POINTER(DrtFrameParams), _f]),
@@ -156,6 +164,7 @@ SIGNATURES = {
     "drt_scene_set_bvh": (C.c_int, [_vp, _vp, C.c_uint32, _u32, C.c_uint32]),
     "drt_scene_upload_device_bvh": (C.c_int, [_vp, _vp]),
     "drt_group_scene_upload_device_bvh": (C.c_int, [_vp, _vp]),
+    "drt_scene_upload_device_bvh_ex": (C.c_int, [_vp, _vp, C.c_int]),
     "drt_scene_new": (_vp, []),
     "drt_scene_load_p3f": (_vp, [C.c_char_p]),
     "drt_scene_free": (None, [_vp]),

@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "drt_bvh_build.hpp"
+#include "drt_bvh_commit.hpp"
 #include "drt_kernels.hpp"
 #include "drt_layout.hpp"
 
@@ -127,6 +128,13 @@ struct drt_ctx {
   hipEvent_t bev[3] = {nullptr, nullptr, nullptr};
   drt_bvh_build_info build_info{};
   bool has_build_info = false;
+  // the device commit (drt_build_bvh_device_commit): its status words on the device and pinned on the host,
+  // events around its kernels; the last commit's figures, whichever side committed
+  DevBuf d_commit_status;
+  PinnedBuf h_commit_status;
+  hipEvent_t cev[2] = {nullptr, nullptr};
+  drt_bvh_commit_info commit_info{};
+  bool has_commit_info = false;
   // BVH
   bool has_bvh = false;
   DevBuf d_nodes, d_big;
@@ -659,6 +667,8 @@ void drt_destroy(drt_ctx* c) {
     if (e) (void)hipEventDestroy(e);
   for (auto& e : c->bev)
     if (e) (void)hipEventDestroy(e);
+  for (auto& e : c->cev)
+    if (e) (void)hipEventDestroy(e);
   for (int k = 0; k < DRT_FRAME_SLOTS; k++) {
     if (c->aux[k]) {
       (void)hipStreamSynchronize(c->aux[k]);
@@ -927,12 +937,78 @@ int drt_upload_bvh(drt_ctx* c, const drt_bvh_node* nodes, uint32_t n_nodes, cons
   std::vector<PrimRecord> perm(n_obj);
   for (uint32_t i = 0; i < n_obj; i++) perm[i] = c->prims_scene[order[i]];
   DRT_HIP(c, hipMemcpy(c->d_prims.p, perm.data(), sizeof(PrimRecord) * perm.size(), hipMemcpyHostToDevice));
+  c->commit_info = drt_bvh_commit_info{0u, c->has_wide ? 1u : 0u, n_slots, c->has_wide ? c->n_wide : 0u};
+  c->has_commit_info = true;
   c->has_bvh = true;
   c->has_grid = false;
   return DRT_OK;
 }
 
-int drt_build_bvh_device(drt_ctx* c, drt_bvh_node* nodes_out, uint32_t* order_out, drt_bvh_build_info* info) {
+// The device commit (drt_bvh_commit.hip) of the tree launch_bvh_build left in d_build_nodes / d_build_order:
+// d_nodes, d_wnodes, d_wleaf, d_prims and the context fields drt_upload_bvh sets, with one 64-B copy back.
+static int commit_bvh_device(drt_ctx* c, uint32_t n, uint32_t n_nodes, uint32_t n_leaves, uint32_t depth,
+                             double* commit_ms) {
+  if ((int)depth >= kMaxBvhDepth)
+    DRT_FAIL(c, DRT_E_UNSUPPORTED, "BVH depth %d exceeds the %d-entry traversal stack", (int)depth, kMaxBvhDepth);
+  const size_t n_inner = n_leaves - 1;
+  const bool wide = env_int("DRT_WIDE_SHADOW", 1) != 0;
+  for (auto& e : c->cev)
+    if (!e) DRT_HIP(c, hipEventCreate(&e));
+  DRT_HIP(c, c->d_nodes.ensure(sizeof(NodeRecord) * std::max<size_t>(1, 2 * n_inner)));
+  DRT_HIP(c, c->d_wnodes.ensure(sizeof(WideNodeRecord4) * std::max<size_t>(1, n_inner)));
+  DRT_HIP(c, c->d_wleaf.ensure(sizeof(LeafBoxRecord) * ((size_t)n + 2)));
+  DRT_HIP(c, c->d_big.ensure(sizeof(uint2)));  // leaves of one or two primitives: no big-leaf table
+  DRT_HIP(c, c->d_commit_status.ensure(sizeof(BvhCommitStatus)));
+  DRT_HIP(c, c->h_commit_status.ensure(sizeof(BvhCommitStatus)));
+  BvhCommitArgs a{};
+  a.nodes = c->d_build_nodes.as<drt_bvh_node>();
+  a.order = c->d_build_order.as<uint32_t>();
+  a.prims_raw = c->d_prims_raw.as<drt_prim>();
+  a.n_prims = n;
+  a.n_nodes = n_nodes;
+  a.depth = depth;
+  a.default_material = (uint32_t)c->mats.size() - 1u;
+  a.wide = wide ? 1 : 0;
+  a.max_wide_levels = kWideMaxStack / (kWideK - 1) + 1;
+  a.scratch = c->d_build.p;
+  a.recs = c->d_nodes.as<NodeRecord>();
+  a.wide_recs = c->d_wnodes.as<WideNodeRecord4>();
+  a.leaf_boxes = c->d_wleaf.as<LeafBoxRecord>();
+  a.prims = c->d_prims.as<PrimRecord>();
+  a.status = c->d_commit_status.as<BvhCommitStatus>();
+  hipStream_t st = c->stream;
+  DRT_HIP(c, hipEventRecord(c->cev[0], st));
+  DRT_HIP(c, launch_bvh_commit(a, st));
+  DRT_HIP(c, hipEventRecord(c->cev[1], st));
+  const BvhCommitStatus* hs = (const BvhCommitStatus*)c->h_commit_status.p;
+  DRT_HIP(c, hipMemcpyAsync(c->h_commit_status.p, c->d_commit_status.p, sizeof(BvhCommitStatus), hipMemcpyDeviceToHost, st));
+  DRT_HIP(c, hipStreamSynchronize(st));
+  float ms = 0.f;
+  DRT_HIP(c, hipEventElapsedTime(&ms, c->cev[0], c->cev[1]));
+  *commit_ms = ms;
+  const uint32_t n_slots = 2u * hs->n_lines;
+  if (n_slots > 2 * n_inner || (n_inner > 0 && n_slots < n_inner) || (wide && hs->n_wide > n_inner))
+    DRT_FAIL(c, DRT_E_HIP, "the device commit returned %u record slots, %u wide records for %zu inner nodes", n_slots,
+             hs->n_wide, n_inner);
+  c->bvh_depth = (int)depth;
+  memcpy(c->root_box, hs->root_box, sizeof(c->root_box));
+  c->root_desc = hs->root_desc;
+  c->has_wide = wide && n_inner > 0 && hs->flags == 0u && hs->n_wide > 0 &&
+                (kWideK - 1) * (int)hs->wide_depth <= kWideMaxStack;
+  if (c->has_wide) {
+    c->wroot = 0;  // the root is the first mark in node-slot order
+    c->n_wide = hs->n_wide;
+  }
+  c->commit_info = drt_bvh_commit_info{1u, c->has_wide ? 1u : 0u, n_slots, c->has_wide ? c->n_wide : 0u};
+  c->has_commit_info = true;
+  c->has_bvh = true;
+  c->has_grid = false;
+  return DRT_OK;
+}
+
+// drt_build_bvh_device and drt_build_bvh_device_commit: the build, then the host or the device commit
+static int build_bvh_device(drt_ctx* c, drt_bvh_node* nodes_out, uint32_t* order_out, drt_bvh_build_info* info,
+                            bool device_commit) {
   if (!c) return DRT_E_INVALID;
   if (!c->has_scene) DRT_FAIL(c, DRT_E_STATE, "upload the scene before building its BVH");
   if (c->n_prims <= 0) DRT_FAIL(c, DRT_E_INVALID, "a scene without primitives has no BVH");
@@ -944,12 +1020,19 @@ int drt_build_bvh_device(drt_ctx* c, drt_bvh_node* nodes_out, uint32_t* order_ou
     if (!e) DRT_HIP(c, hipEventCreate(&e));
   const size_t max_nodes = 2 * (size_t)n - 1;
   DRT_HIP(c, c->d_prims_raw.ensure(sizeof(drt_prim) * n));
-  DRT_HIP(c, c->d_build.fit(bvh_build_scratch_bytes(n)));
+  // The device commit needs DRT_NODE_LAYOUT=1, DRT_WIDE_ORDER=2 and 4-ary records: otherwise the host commits
+  // (drt_get_bvh_commit_info then reports on_device = 0).
+  device_commit = device_commit && env_int("DRT_NODE_LAYOUT", 1) == 1 && env_int("DRT_WIDE_ORDER", 2) == 2 && kWideK == 4;
+  const bool fetch = !device_commit || nodes_out || order_out;
+  // the commit's scratch overlays the builder's, which is free once the build has ended
+  DRT_HIP(c, c->d_build.fit(std::max(bvh_build_scratch_bytes(n), device_commit ? bvh_commit_scratch_bytes(n) : 0)));
   DRT_HIP(c, c->d_build_nodes.fit(sizeof(drt_bvh_node) * max_nodes));
   DRT_HIP(c, c->d_build_order.fit(sizeof(uint32_t) * n));
   DRT_HIP(c, c->d_build_info.ensure(sizeof(uint32_t) * 4));
-  DRT_HIP(c, c->h_build_nodes.ensure(sizeof(drt_bvh_node) * max_nodes));
-  DRT_HIP(c, c->h_build_order.ensure(sizeof(uint32_t) * n));
+  if (fetch) {
+    DRT_HIP(c, c->h_build_nodes.ensure(sizeof(drt_bvh_node) * max_nodes));
+    DRT_HIP(c, c->h_build_order.ensure(sizeof(uint32_t) * n));
+  }
   DRT_HIP(c, c->h_build_info.ensure(sizeof(uint32_t) * 4));
   hipStream_t st = c->stream;
   DRT_HIP(c, hipEventRecord(c->bev[0], st));
@@ -968,28 +1051,52 @@ int drt_build_bvh_device(drt_ctx* c, drt_bvh_node* nodes_out, uint32_t* order_ou
     DRT_FAIL(c, DRT_E_HIP, "the device build returned %u nodes, %u leaves for %u objects", n_nodes, n_leaves, n);
   drt_bvh_node* hn = (drt_bvh_node*)c->h_build_nodes.p;
   uint32_t* ho = (uint32_t*)c->h_build_order.p;
-  DRT_HIP(c, hipMemcpyAsync(hn, c->d_build_nodes.p, sizeof(drt_bvh_node) * n_nodes, hipMemcpyDeviceToHost, st));
-  DRT_HIP(c, hipMemcpyAsync(ho, c->d_build_order.p, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, st));
-  DRT_HIP(c, hipEventRecord(c->bev[2], st));
-  DRT_HIP(c, hipStreamSynchronize(st));
   float build_ms = 0.f, fetch_ms = 0.f;
+  if (fetch) {
+    DRT_HIP(c, hipMemcpyAsync(hn, c->d_build_nodes.p, sizeof(drt_bvh_node) * n_nodes, hipMemcpyDeviceToHost, st));
+    DRT_HIP(c, hipMemcpyAsync(ho, c->d_build_order.p, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, st));
+    DRT_HIP(c, hipEventRecord(c->bev[2], st));
+    DRT_HIP(c, hipStreamSynchronize(st));
+    DRT_HIP(c, hipEventElapsedTime(&fetch_ms, c->bev[1], c->bev[2]));
+  }
   DRT_HIP(c, hipEventElapsedTime(&build_ms, c->bev[0], c->bev[1]));
-  DRT_HIP(c, hipEventElapsedTime(&fetch_ms, c->bev[1], c->bev[2]));
-  const auto t0 = std::chrono::steady_clock::now();
-  const int rc = drt_upload_bvh(c, hn, n_nodes, ho, n);
-  if (rc) return rc;
+  double commit_ms = 0.0;
+  if (device_commit) {
+    const int rc = commit_bvh_device(c, n, n_nodes, n_leaves, depth, &commit_ms);
+    if (rc) return rc;
+  } else {
+    const auto t0 = std::chrono::steady_clock::now();
+    const int rc = drt_upload_bvh(c, hn, n_nodes, ho, n);
+    if (rc) return rc;
+    commit_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  }
   drt_bvh_build_info bi{};
   bi.n_nodes = n_nodes;
   bi.n_leaves = n_leaves;
   bi.depth = depth;
   bi.build_ms = build_ms;
   bi.fetch_ms = fetch_ms;
-  bi.commit_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  bi.commit_ms = commit_ms;
   c->build_info = bi;
   c->has_build_info = true;
   if (nodes_out) memcpy(nodes_out, hn, sizeof(drt_bvh_node) * n_nodes);
   if (order_out) memcpy(order_out, ho, sizeof(uint32_t) * n);
   if (info) *info = bi;
+  return DRT_OK;
+}
+
+int drt_build_bvh_device(drt_ctx* c, drt_bvh_node* nodes_out, uint32_t* order_out, drt_bvh_build_info* info) {
+  return build_bvh_device(c, nodes_out, order_out, info, false);
+}
+
+int drt_build_bvh_device_commit(drt_ctx* c, drt_bvh_node* nodes_out, uint32_t* order_out, drt_bvh_build_info* info) {
+  return build_bvh_device(c, nodes_out, order_out, info, true);
+}
+
+int drt_get_bvh_commit_info(const drt_ctx* c, drt_bvh_commit_info* info) {
+  if (!c || !info) return DRT_E_INVALID;
+  if (!c->has_commit_info || !c->has_bvh) return DRT_E_STATE;
+  *info = c->commit_info;
   return DRT_OK;
 }
 

@@ -300,6 +300,25 @@ int drt_scene_upload_device_bvh(drt_ctx* ctx, drt_scene* s) {
   return drt_scene_set_bvh(s, nodes.data(), info.n_nodes, order.data(), (uint32_t)n);
 }
 
+int drt_scene_upload_device_bvh_ex(drt_ctx* ctx, drt_scene* s, int flags) {
+  if (flags & ~(DRT_BVH_COMMIT_DEVICE | DRT_BVH_NO_INSTALL)) return DRT_E_INVALID;
+  if (flags == 0) return drt_scene_upload_device_bvh(ctx, s);
+  int rc = upload_for_device_build(ctx, s);
+  if (rc) return rc;
+  const size_t n = (size_t)s->scene.getNumObjects();
+  if (n == 0) return DRT_E_INVALID;
+  const bool install = !(flags & DRT_BVH_NO_INSTALL);
+  std::vector<drt_bvh_node> nodes(install ? 2 * n - 1 : 0);
+  std::vector<uint32_t> order(install ? n : 0);
+  drt_bvh_node* np = install ? nodes.data() : nullptr;
+  uint32_t* op = install ? order.data() : nullptr;
+  drt_bvh_build_info info;
+  rc = (flags & DRT_BVH_COMMIT_DEVICE) ? drt_build_bvh_device_commit(ctx, np, op, &info)
+                                       : drt_build_bvh_device(ctx, np, op, &info);
+  if (rc || !install) return rc;
+  return drt_scene_set_bvh(s, np, info.n_nodes, op, (uint32_t)n);
+}
+
 int drt_group_scene_upload_device_bvh(drt_group* g, drt_scene* s) {
   if (!g || !s) return DRT_E_INVALID;
   int rc = drt_scene_upload_device_bvh(drt_group_ctx(g, 0), s);  // built once, on rank 0

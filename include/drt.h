@@ -227,6 +227,23 @@ typedef struct {
 int drt_build_bvh_device(drt_ctx* ctx, drt_bvh_node* nodes_out, uint32_t* order_out, drt_bvh_build_info* info);
 /* The figures of the context's last drt_build_bvh_device (DRT_E_STATE before one). */
 int drt_get_bvh_build_info(const drt_ctx* ctx, drt_bvh_build_info* info);
+/* drt_build_bvh_device with the commit on the device too (csrc/hip/drt_bvh_commit.hip): the inner records and
+ * their placement in 128-B lines, the leaf boxes, the primitive records in tree order and the 4-ary shadow
+ * tree are written by HIP kernels from the builder's output, and every query answers and counts exactly as
+ * after the host commit of the same tree; only where a record sits in memory differs.  With nodes_out and
+ * order_out both NULL the tree never leaves the device: 64 B of status words are all that is copied back, and
+ * info->fetch_ms is 0.  info->commit_ms is the device time of the commit kernels (HIP events).  The host
+ * commits instead (and drt_get_bvh_commit_info says so) under DRT_NODE_LAYOUT != 1, DRT_WIDE_ORDER != 2 or a
+ * library built with DRT_WIDE8.  Errors as drt_build_bvh_device. */
+int drt_build_bvh_device_commit(drt_ctx* ctx, drt_bvh_node* nodes_out, uint32_t* order_out, drt_bvh_build_info* info);
+typedef struct {
+  uint32_t on_device; /* 1: committed by the device kernels, 0: by the host (drt_upload_bvh)          */
+  uint32_t has_wide;  /* the tree has a 4-ary shadow tree                                              */
+  uint32_t n_slots;   /* 64-B inner record slots, padding slots included                              */
+  uint32_t n_wide;    /* 4-ary records (0 without a shadow tree)                                       */
+} drt_bvh_commit_info;
+/* The context's last BVH commit, by drt_upload_bvh or on the device (DRT_E_STATE without a committed BVH). */
+int drt_get_bvh_commit_info(const drt_ctx* ctx, drt_bvh_commit_info* info);
 int drt_upload_grid(drt_ctx* ctx, const int32_t dims[3], const float bmin[3], const float bmax[3],
                     const int64_t* cell_start /* nx*ny*nz+1 */, const int32_t* cell_objs, int64_t n_refs);
 /* Optional, after drt_upload_grid: a BVH of the same objects (the BVH::Build result, as drt_upload_bvh

@@ -94,6 +94,13 @@ int drt_scene_set_bvh(drt_scene* s, const drt_bvh_node* nodes, uint32_t n_nodes,
  * host arrays on every rank with drt_upload_bvh. */
 int drt_scene_upload_device_bvh(drt_ctx* ctx, drt_scene* s);
 int drt_group_scene_upload_device_bvh(drt_group* g, drt_scene* s);
+/* drt_scene_upload_device_bvh with flags (0: the same call).  DRT_BVH_COMMIT_DEVICE commits on the device
+ * (drt_build_bvh_device_commit).  DRT_BVH_NO_INSTALL skips the fetch of the tree and drt_scene_set_bvh: the
+ * host scene is not marked built by this call, so drt_scene_trace_cpu and drt_scene_bvh_export behave as on
+ * an unbuilt scene (they build, or keep, the host's own tree, which is not the one the device walks).  Other
+ * flag bits are DRT_E_INVALID.  The group form keeps the host commit. */
+enum { DRT_BVH_COMMIT_DEVICE = 1, DRT_BVH_NO_INSTALL = 2 };
+int drt_scene_upload_device_bvh_ex(drt_ctx* ctx, drt_scene* s, int flags);
 /* The scene's current camera frame to a context / every device of a group (drt_set_camera): the
  * per-frame camera of the interactive renderer (main.cpp:530-533) with the scene resident. */
 int drt_scene_upload_camera(drt_ctx* ctx, const drt_scene* s);

@@ -1,17 +1,20 @@
 """The two BVH builders on the headline scene (bench.py's 1M triangles plus floor, 512x512 at 64 spp):
 the host's binned-SAH build (drt_scene_build, tree-identical to the reference) against the device LBVH
-(drt_build_bvh_device), and the headline frame on either tree.
+(drt_build_bvh_device) committed by the host, and the same LBVH committed on the device
+(drt_build_bvh_device_commit) with and without installing the tree in the host scene; the headline frame on
+each committed tree.
 
 Two JSON lines:
   builds  --rounds interleaved rounds after one warm-up round, each on a fresh Scene: the host build's ms
           (host clock around drt_scene_build) and the device build's three drt_bvh_build_info times (HIP
-          events around the kernels and around the fetch, host clock around the drt_upload_bvh commit), plus
-          the host clock around each whole upload call;
-  frames  two contexts in one process, one per tree, alternating frame by frame: device ms of the frame
+          events around the kernels and around the fetch, host clock around the drt_upload_bvh commit — HIP
+          events around the commit kernels in the dcommit arms), plus the host clock around each whole upload
+          call; arms: device (host commit), dcommit (device commit), dcommit_noinstall (install=False);
+  frames  one context per arm in one process, alternating frame by frame: device ms of the frame
           (HIP events), Mrays/s = (closest + shadow traversals of a stats frame) / median ms, the
           shadow-query stream's ms (drt_frame_stage_times) and the binary tree's depth.
 
-  python tools/bvh_build_ab.py [--rounds 10] [--tris 1000000] > profiles/gpu_bvh_build.jsonl
+  python tools/bvh_build_ab.py [--rounds 10] [--tris 1000000] > profiles/gpu_bvh_commit.jsonl
 """
 import argparse
 import json
@@ -58,9 +61,10 @@ def main():
         bench.populate(s, tris, args.res, args.spp)
         return s
 
-    ctx = {"host": drt.Renderer(0), "device": drt.Renderer(0)}
-    rows = {"host_build_ms": [], "host_upload_wall_ms": [], "device_build_ms": [], "device_fetch_ms": [],
-            "device_commit_ms": [], "device_upload_wall_ms": []}
+    dev_arms = {"device": {}, "dcommit": {"commit": "device"}, "dcommit_noinstall": {"commit": "device", "install": False}}
+    ctx = {a: drt.Renderer(0) for a in ("host", *dev_arms)}
+    rows = {"host_build_ms": [], "host_upload_wall_ms": []}
+    rows.update({f"{a}_{k}_ms": [] for a in dev_arms for k in ("build", "fetch", "commit", "upload_wall")})
     scenes = {}
     for rnd in range(args.rounds + 1):  # round 0 warms both arms up (code objects, allocations, pinned buffers)
         s = fresh()
@@ -69,27 +73,30 @@ def main():
         t1 = time.perf_counter()
         ctx["host"].upload(s)
         t2 = time.perf_counter()
-        d = fresh()
-        t3 = time.perf_counter()
-        ctx["device"].upload(d, build="device")
-        t4 = time.perf_counter()
-        scenes = {"host": s, "device": d}
-        if rnd == 0:
-            continue
-        bi = ctx["device"].bvh_build_info()
-        rows["host_build_ms"].append((t1 - t0) * 1e3)
-        rows["host_upload_wall_ms"].append((t2 - t0) * 1e3)
-        rows["device_build_ms"].append(bi["build_ms"])
-        rows["device_fetch_ms"].append(bi["fetch_ms"])
-        rows["device_commit_ms"].append(bi["commit_ms"])
-        rows["device_upload_wall_ms"].append((t4 - t3) * 1e3)
+        scenes = {"host": s}
+        if rnd:
+            rows["host_build_ms"].append((t1 - t0) * 1e3)
+            rows["host_upload_wall_ms"].append((t2 - t0) * 1e3)
+        for a, kw in dev_arms.items():
+            d = fresh()
+            t3 = time.perf_counter()
+            ctx[a].upload(d, build="device", **kw)
+            t4 = time.perf_counter()
+            scenes[a] = d
+            if rnd == 0:
+                continue
+            bi = ctx[a].bvh_build_info()
+            for k in ("build", "fetch", "commit"):
+                rows[f"{a}_{k}_ms"].append(bi[f"{k}_ms"])
+            rows[f"{a}_upload_wall_ms"].append((t4 - t3) * 1e3)
     out = {"record": "builds", "objects": int(scenes["host"].info().n_objects), "rounds": args.rounds}
     out.update({k: spread(v) for k, v in rows.items()})
     out["host_build_over_device_build_plus_fetch"] = round(
         out["host_build_ms"]["median"] / (out["device_build_ms"]["median"] + out["device_fetch_ms"]["median"]), 1)
+    out["commit_info"] = {a: ctx[a].bvh_commit_info() for a in dev_arms}
     print(json.dumps(out), flush=True)
 
-    arms = ("host", "device")
+    arms = tuple(ctx)
     rays, ms, stream = {}, {a: [] for a in arms}, {a: [] for a in arms}
     for a in arms:
         ctx[a].render(seed=7, stats=True)
@@ -108,9 +115,16 @@ def main():
     for a in arms:
         m = spread(ms[a])
         out[a] = {"frame_ms": m, "mrays_s": round(rays[a] / m["median"] / 1e3, 1), "rays": int(rays[a]),
-                  "trace_stream_ms": spread(stream[a]), "bvh_depth": tree_depth(scenes[a].bvh_export()),
-                  "bvh_nodes": int(scenes[a].info().bvh_nodes)}
-    out["device_over_host_frame_rate"] = round(out["host"]["frame_ms"]["median"] / out["device"]["frame_ms"]["median"], 3)
+                  "trace_stream_ms": spread(stream[a])}
+        if a == "host":
+            out[a].update(bvh_depth=tree_depth(scenes[a].bvh_export()), bvh_nodes=int(scenes[a].info().bvh_nodes))
+        else:  # (a scene without the tree installed has none to export)
+            bi = ctx[a].bvh_build_info()
+            out[a].update(bvh_depth=bi["depth"], bvh_nodes=bi["n_nodes"])
+    for a in dev_arms:
+        out[f"{a}_over_host_frame_rate"] = round(out["host"]["frame_ms"]["median"] / out[a]["frame_ms"]["median"], 3)
+    out["dcommit_over_device_frame_rate"] = round(
+        out["device"]["frame_ms"]["median"] / out["dcommit"]["frame_ms"]["median"], 3)
     print(json.dumps(out), flush=True)
     for r in ctx.values():
         r.close()
