@@ -193,6 +193,17 @@ class Scene:
         check(_lib.load().drt_scene_set_bvh(self.h, nodes.ctypes.data, len(nodes), o.ctypes.data_as(_lib._u32),
                                             len(o)), what="drt_scene_set_bvh")
 
+    def set_grid(self, dims, bmin, bmax, cell_start, cell_objs):
+        """drt_scene_set_grid, the inverse of grid_export: install cell lists (e.g. a device-built grid's) as
+        the scene's grid; trace_cpu, grid_export and upload then use them.  Refused (DRT_E_INVALID) unless
+        the starts are monotone over nx*ny*nz + 1 entries and every index is an object of the scene."""
+        d = np.ascontiguousarray(dims, np.int32)
+        cs = np.ascontiguousarray(cell_start, np.int64)
+        co = np.ascontiguousarray(cell_objs, np.int32)
+        check(_lib.load().drt_scene_set_grid(self.h, d.ctypes.data_as(_lib._i32), _fp(_f32(bmin)), _fp(_f32(bmax)),
+                                             cs.ctypes.data_as(_lib._i64), len(cs), co.ctypes.data_as(_lib._i32),
+                                             len(co)), what="drt_scene_set_grid")
+
     def trace_cpu(self, rays, shadow=False):
         """The scalar host path (BVH::Traverse / Grid::Traverse / the NONE scan on the CPU, one ray
         at a time): closest -> (t, normal, object); shadow -> occluded (uint8)."""
@@ -270,7 +281,11 @@ class Renderer:
         build, slower to trace (README.md, Use).  With build="device", commit="device" also lays out the
         records and the shadow tree by HIP kernels (drt_build_bvh_device_commit; the same answers and
         traversal counts), and install=False leaves `scene` without the tree: nothing but status words
-        comes back from the device, and scene.trace_cpu / scene.bvh_export behave as on an unbuilt scene."""
+        comes back from the device, and scene.trace_cpu / scene.bvh_export behave as on an unbuilt scene.
+        A Grid scene with build="device" gets its grid from HIP kernels too (drt_build_grid_device): exactly
+        the host's cell lists, bit for bit, committed by drt_upload_grid (commit="host") or by kernels
+        (commit="device").  No shadow tree is built for it: shadow queries take the Grid walk, which renders
+        the same frame at a lower rate."""
         if build not in ("host", "device"):
             raise ValueError(f"build must be 'host' or 'device', not {build!r}")
         if commit not in ("host", "device"):
@@ -279,6 +294,10 @@ class Renderer:
             raise ValueError("commit='device' and install=False need build='device'")
         if build == "host":
             check(_lib.load().drt_scene_upload(self.h, scene.h), self.h, "drt_scene_upload")
+        elif scene.info().accel == ACCEL["grid"]:
+            flags = (_lib.GRID_COMMIT_DEVICE if commit == "device" else 0) | (0 if install else _lib.GRID_NO_INSTALL)
+            check(_lib.load().drt_scene_upload_device_grid(self.h, scene.h, flags), self.h,
+                  "drt_scene_upload_device_grid")
         elif commit == "host" and install:
             check(_lib.load().drt_scene_upload_device_bvh(self.h, scene.h), self.h, "drt_scene_upload_device_bvh")
         else:
@@ -294,6 +313,15 @@ class Renderer:
         i = _lib.DrtBvhCommitInfo()
         check(_lib.load().drt_get_bvh_commit_info(self.h, C.byref(i)), self.h, "drt_get_bvh_commit_info")
         return {n: int(getattr(i, n)) for n, _ in i._fields_}
+
+    def grid_build_info(self):
+        """drt_grid_build_info of the last build="device" upload of a Grid scene: dims, box, cells,
+        references, the build / fetch / commit times in ms and whether the device committed."""
+        i = _lib.DrtGridBuildInfo()
+        check(_lib.load().drt_get_grid_build_info(self.h, C.byref(i)), self.h, "drt_get_grid_build_info")
+        out = {n: getattr(i, n) for n, _ in i._fields_ if n != "reserved"}
+        return {k: (tuple(v) if k in ("dims", "bmin", "bmax") else (float(v) if k.endswith("_ms") else int(v)))
+                for k, v in out.items()}
 
     def bvh_build_info(self):
         """drt_bvh_build_info of the last build="device" upload: nodes, leaves, depth and the build /
@@ -498,7 +526,10 @@ class RendererGroup:
         arrays are committed on every device."""
         if build not in ("host", "device"):
             raise ValueError(f"build must be 'host' or 'device', not {build!r}")
-        if build == "device":
+        if build == "device" and scene.info().accel == ACCEL["grid"]:
+            self._check(_lib.load().drt_group_scene_upload_device_grid(self.h, scene.h),
+                        "drt_group_scene_upload_device_grid")
+        elif build == "device":
             self._check(_lib.load().drt_group_scene_upload_device_bvh(self.h, scene.h),
                         "drt_group_scene_upload_device_bvh")
         else:

@@ -115,6 +115,14 @@ class DrtBvhCommitInfo(C.Structure):
 
 
 BVH_COMMIT_DEVICE, BVH_NO_INSTALL = 1, 2  # drt_scene_upload_device_bvh_ex flags (include/drt_host.h)
+GRID_COMMIT_DEVICE, GRID_NO_INSTALL = 1, 2  # drt_scene_upload_device_grid flags (include/drt.h, drt_host.h)
+
+
+class DrtGridBuildInfo(C.Structure):
+    _fields_ = [("dims", C.c_int32 * 3), ("bmin", C.c_float * 3), ("bmax", C.c_float * 3), ("n_cells", C.c_int64),
+                ("n_refs", C.c_int64), ("build_ms", C.c_double), ("fetch_ms", C.c_double), ("commit_ms", C.c_double),
+                ("on_device", C.c_uint32), ("reserved", C.c_uint32)]
+
 
 # Every symbol include/drt.h and include/drt_host.h declare, with its ctypes signature.
 SIGNATURES = {
@@ -131,6 +139,9 @@ SIGNATURES = {
     "drt_build_bvh_device_commit": (C.c_int, [_vp, _vp, _u32, C.POINTER(DrtBvhBuildInfo)]),
     "drt_get_bvh_commit_info": (C.c_int, [_vp, C.POINTER(DrtBvhCommitInfo)]),
     "drt_upload_grid": (C.c_int, [_vp, _i32, _f, _f, _i64, _i32, C.c_int64]),
+    "drt_build_grid_device": (C.c_int, [_vp, C.c_float, C.c_int, C.POINTER(DrtGridBuildInfo)]),
+    "drt_fetch_grid_device": (C.c_int, [_vp, _i64, _i32]),
+    "drt_get_grid_build_info": (C.c_int, [_vp, C.POINTER(DrtGridBuildInfo)]),
     "drt_upload_grid_shadow_bvh": (C.c_int, [_vp, _vp, C.c_uint32, _u32, C.c_uint32]),
     "drt_render": (C.c_int, [_vp, C.POINTER(DrtFrameParams), _f]),
     "drt_shard_layout": (C.c_int, [_vp, C.POINTER(DrtFrameParams), _i64, _i64]),
@@ -165,6 +176,9 @@ SIGNATURES = {
     "drt_scene_upload_device_bvh": (C.c_int, [_vp, _vp]),
     "drt_group_scene_upload_device_bvh": (C.c_int, [_vp, _vp]),
     "drt_scene_upload_device_bvh_ex": (C.c_int, [_vp, _vp, C.c_int]),
+    "drt_scene_set_grid": (C.c_int, [_vp, _i32, _f, _f, _i64, C.c_int64, _i32, C.c_int64]),
+    "drt_scene_upload_device_grid": (C.c_int, [_vp, _vp, C.c_int]),
+    "drt_group_scene_upload_device_grid": (C.c_int, [_vp, _vp]),
     "drt_scene_new": (_vp, []),
     "drt_scene_load_p3f": (_vp, [C.c_char_p]),
     "drt_scene_free": (None, [_vp]),

@@ -22,6 +22,7 @@
 
 #include "../../../include/drt.h"
 #include "drt_bvh_build.hpp"
+#include "drt_prim_device.hpp"
 
 namespace drt {
 
@@ -97,16 +98,6 @@ Arena carve(void* scratch, uint32_t n, size_t* total) {
 __device__ inline float smin(float a, float b) { return (b < a) ? b : a; }  // std::min, as drt_accel.cpp
 __device__ inline float smax(float a, float b) { return (a < b) ? b : a; }  // std::max
 
-// float -> unsigned whose order is the float's (negative floats below positive ones)
-__device__ inline uint32_t ordered(float f) {
-  const uint32_t u = __float_as_uint(f);
-  return u ^ ((u >> 31) ? 0xFFFFFFFFu : 0x80000000u);
-}
-__device__ inline float unordered(uint32_t o) {
-  return __uint_as_float(o ^ ((o >> 31) ? 0x80000000u : 0xFFFFFFFFu));
-}
-__device__ inline bool finite(float f) { return (__float_as_uint(f) & 0x7F800000u) != 0x7F800000u; }
-
 // Exclusive scan of one value per thread over the 256 threads of the workgroup (wave scans by cross-lane
 // shifts, the four wave totals through LDS); every thread gets the workgroup's total.
 __device__ inline uint32_t block_scan_excl(uint32_t v, uint32_t* wave_tot /* LDS, 4 words */, uint32_t& total) {
@@ -147,29 +138,7 @@ __global__ __launch_bounds__(kThreads) void bvh_prim_bounds(const drt_prim* __re
   const bool valid = i < n;
   if (valid) {
     const drt_prim p = prims[i];
-    if (p.type == DRT_PRIM_TRIANGLE) {  // Triangle::Triangle, drt_scene.cpp:18-33
-#pragma unroll
-      for (int a = 0; a < 3; a++) {
-        float mn = 3.402823466e+38f, mx = -3.402823466e+38f;
-        const float v[3] = {p.a[a], p.b[a], p.c[a]};
-#pragma unroll
-        for (int k = 0; k < 3; k++) {
-          if (v[k] < mn) mn = v[k];
-          if (v[k] > mx) mx = v[k];
-        }
-        lo[a] = mn - 0.001f;
-        hi[a] = mx + 0.001f;
-      }
-    } else if (p.type == DRT_PRIM_SPHERE) {
-#pragma unroll
-      for (int a = 0; a < 3; a++) { lo[a] = p.a[a] - p.r; hi[a] = p.a[a] + p.r; }
-    } else if (p.type == DRT_PRIM_BOX) {
-#pragma unroll
-      for (int a = 0; a < 3; a++) { lo[a] = p.a[a]; hi[a] = p.b[a]; }
-    } else {  // a plane keeps the default box (scene.h:116)
-#pragma unroll
-      for (int a = 0; a < 3; a++) { lo[a] = -1.f; hi[a] = 1.f; }
-    }
+    prim_bounds(p, lo, hi);
     A.pbox[2 * (size_t)i] = make_float4(lo[0], lo[1], lo[2], 0.f);
     A.pbox[2 * (size_t)i + 1] = make_float4(hi[0], hi[1], hi[2], 0.f);
   }

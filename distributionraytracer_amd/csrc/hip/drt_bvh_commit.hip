@@ -34,6 +34,7 @@
 #include <cstdint>
 
 #include "drt_bvh_commit.hpp"
+#include "drt_prim_device.hpp"
 
 namespace drt {
 
@@ -274,22 +275,8 @@ __global__ __launch_bounds__(kThreads) void commit_leaf_prims(const drt_bvh_node
   if (i >= n) return;
   const uint32_t o = order[i];
   if (o >= n) return;
-  // drt_prim as three 16-B words: (type, material, a.x, a.y), (a.z, b.x, b.y, b.z), (c.x, c.y, c.z, r)
-  const float4 w0 = raw[3 * (size_t)o], w1 = raw[3 * (size_t)o + 1], w2 = raw[3 * (size_t)o + 2];
-  const uint32_t type = __float_as_uint(w0.x);
-  const int32_t material = (int32_t)__float_as_uint(w0.y);
-  const uint32_t mat = material < 0 ? default_material : (uint32_t)material;
-  const float ax = w0.z, ay = w0.w, az = w1.x;
-  float4 q0 = make_float4(ax, ay, az, __uint_as_float((type & 3u) | (mat << 2)));
-  float4 q1 = make_float4(0.f, 0.f, 0.f, __uint_as_float(o)), q2 = zero;
-  if (type == (uint32_t)DRT_PRIM_TRIANGLE) {  // the edges, as pack_prim subtracts them
-    q1.x = w1.y - ax; q1.y = w1.z - ay; q1.z = w1.w - az;
-    q2.x = w2.x - ax; q2.y = w2.y - ay; q2.z = w2.z - az;
-  } else if (type == (uint32_t)DRT_PRIM_SPHERE || type == (uint32_t)DRT_PRIM_PLANE) {
-    q1.x = w2.w;
-  } else {
-    q1.x = w1.y; q1.y = w1.z; q1.z = w1.w;
-  }
+  float4 q0, q1, q2;
+  pack_prim_record(raw, o, default_material, q0, q1, q2);
   prims[3 * (size_t)i] = q0;
   prims[3 * (size_t)i + 1] = q1;
   prims[3 * (size_t)i + 2] = q2;

@@ -12,8 +12,10 @@
 
 #include "drt_bvh_build.hpp"
 #include "drt_bvh_commit.hpp"
+#include "drt_grid_build.hpp"
 #include "drt_kernels.hpp"
 #include "drt_layout.hpp"
+#include "../../../include/drt_scene.hpp"
 
 namespace drt {
 void launch_path(const SceneArgs& S, const FrameArgs& F, int accel, bool tri_only, bool stats, hipStream_t st);
@@ -135,6 +137,13 @@ struct drt_ctx {
   hipEvent_t cev[2] = {nullptr, nullptr};
   drt_bvh_commit_info commit_info{};
   bool has_commit_info = false;
+  // the device grid builder (drt_build_grid_device): its per-object and per-reference scratch, the objects'
+  // 24-B cell ranges, its status words on the device and pinned on the host, pinned copies of the fetched
+  // lists and ranges, the last build's figures; grid_on_device: the resident grid's lists are the builder's
+  DevBuf d_gb_obj, d_gb_refs, d_gb_ranges, d_gb_status;
+  PinnedBuf h_gb_status, h_gb_start, h_gb_objs, h_gb_ranges;
+  drt_grid_build_info grid_info{};
+  bool has_grid_info = false, grid_on_device = false, grid_cells_valid = false;
   // BVH
   bool has_bvh = false;
   DevBuf d_nodes, d_big;
@@ -1283,8 +1292,224 @@ int drt_upload_grid(drt_ctx* c, const int32_t dims[3], const float bmin[3], cons
   memcpy(c->gmin, bmin, sizeof(c->gmin));
   memcpy(c->gmax, bmax, sizeof(c->gmax));
   c->grid_cells = std::move(cells_of);
+  c->grid_cells_valid = true;
+  c->grid_on_device = false;
   c->has_grid = true;
   c->has_bvh = false;
+  return DRT_OK;
+}
+
+// ---- the device grid builder (drt_grid_build.hip) --------------------------------------------------------
+// device -> pinned host copy of the resident device-built lists and the objects' cell ranges; the ranges
+// become c->grid_cells (what drt_upload_grid derives from the lists)
+static int fetch_grid_device(drt_ctx* c) {
+  const drt_grid_build_info& gi = c->grid_info;
+  const size_t n = (size_t)c->n_prims;
+  DRT_HIP(c, c->h_gb_start.ensure(4 * ((size_t)gi.n_cells + 1)));
+  DRT_HIP(c, c->h_gb_objs.ensure(4 * std::max<size_t>(1, (size_t)gi.n_refs)));
+  DRT_HIP(c, c->h_gb_ranges.ensure(24 * n));
+  hipStream_t st = c->stream;
+  DRT_HIP(c, hipMemcpyAsync(c->h_gb_start.p, c->d_cell_start.p, 4 * ((size_t)gi.n_cells + 1), hipMemcpyDeviceToHost, st));
+  if (gi.n_refs)
+    DRT_HIP(c, hipMemcpyAsync(c->h_gb_objs.p, c->d_cell_objs.p, 4 * (size_t)gi.n_refs, hipMemcpyDeviceToHost, st));
+  DRT_HIP(c, hipMemcpyAsync(c->h_gb_ranges.p, c->d_gb_ranges.p, 24 * n, hipMemcpyDeviceToHost, st));
+  DRT_HIP(c, hipStreamSynchronize(st));
+  c->grid_cells.assign((const int32_t*)c->h_gb_ranges.p, (const int32_t*)c->h_gb_ranges.p + 6 * n);
+  for (size_t i = 0; i < n; i++) {  // an object listed nowhere, as drt_upload_grid marks it
+    int32_t* r = &c->grid_cells[6 * i];
+    if (r[3] < r[0] || r[4] < r[1] || r[5] < r[2]) {
+      r[0] = r[1] = r[2] = INT32_MAX;
+      r[3] = r[4] = r[5] = -1;
+    }
+  }
+  c->grid_cells_valid = true;
+  return DRT_OK;
+}
+
+// the buffers drt_upload_grid fills, written by the kernels of drt_grid_build.hip from the device-resident lists
+static int commit_grid_device(drt_ctx* c, const GridDims& g, uint32_t n_refs, double* commit_ms) {
+  const size_t ncell = (size_t)g.n[0] * g.n[1] * g.n[2];
+  hipStream_t st = c->stream;
+  for (auto& e : c->cev)
+    if (!e) DRT_HIP(c, hipEventCreate(&e));
+  GridCommitArgs a{};
+  a.prims_raw = c->d_prims_raw.as<drt_prim>();
+  a.n_prims = (uint32_t)c->n_prims;
+  a.n_refs = n_refs;
+  a.default_material = (uint32_t)c->mats.size() - 1u;
+  a.g = g;
+  a.cell_start = c->d_cell_start.as<uint32_t>();
+  a.cell_objs = c->d_cell_objs.as<uint32_t>();
+  a.refs_scratch = c->d_gb_refs.p;
+  a.prims = c->d_prims.as<PrimRecord>();
+  a.status = c->d_gb_status.as<GridBuildStatus>();
+  // the macro-cell bitmap, at drt_upload_grid's rule
+  int ms = 0;
+  auto mdim = [&](int d, int m) { return (d + (1 << m) - 1) >> m; };
+  while ((size_t)mdim(g.n[0], ms) * mdim(g.n[1], ms) * mdim(g.n[2], ms) > kMacroBits) ms++;
+  const int mx = mdim(g.n[0], ms), my = mdim(g.n[1], ms), mz = mdim(g.n[2], ms);
+  const size_t words = ((size_t)mx * my * mz + 31) / 32;
+  DRT_HIP(c, c->d_macro.ensure(4 * words));
+  a.macro = c->d_macro.as<uint32_t>();
+  a.macro_shift = ms;
+  a.macro_dim[0] = mx;
+  a.macro_dim[1] = my;
+  DRT_HIP(c, hipEventRecord(c->cev[0], st));
+  DRT_HIP(c, hipMemsetAsync(c->d_macro.p, 0, 4 * words, st));
+  if (c->tri_only) {
+    DRT_HIP(c, c->d_cell_tpos.ensure(4 * (ncell + 1)));
+    a.tpos = c->d_cell_tpos.as<uint32_t>();
+    DRT_HIP(c, launch_grid_commit_tpos(a, st));
+    const GridBuildStatus* hs = (const GridBuildStatus*)c->h_gb_status.p;
+    DRT_HIP(c, hipMemcpyAsync(c->h_gb_status.p, c->d_gb_status.p, sizeof(GridBuildStatus), hipMemcpyDeviceToHost, st));
+    DRT_HIP(c, hipStreamSynchronize(st));
+    const uint64_t pos = hs->scan_total;
+    if (pos >= 0x80000000ull) DRT_FAIL(c, DRT_E_UNSUPPORTED, "too many grid references");
+    const size_t bytes = 4 * (size_t)(pos / 2 + 1) * 20 + kPrimPadBytes;
+    DRT_HIP(c, c->d_cell_tris.ensure(bytes));
+    DRT_HIP(c, hipMemsetAsync(c->d_cell_tris.p, 0, bytes, st));  // the padding slots and the tail
+    a.tris = c->d_cell_tris.as<float>();
+    c->d_cell_recs.release();
+  } else {
+    c->d_cell_tris.release();
+    c->d_cell_tpos.release();
+    const size_t bytes = sizeof(PrimRecord) * std::max<size_t>(1, n_refs) + kPrimPadBytes;
+    DRT_HIP(c, c->d_cell_recs.ensure(bytes));
+    DRT_HIP(c, hipMemsetAsync(c->d_cell_recs.p, 0, bytes, st));
+    a.recs = c->d_cell_recs.as<PrimRecord>();
+  }
+  DRT_HIP(c, launch_grid_commit(a, st));
+  DRT_HIP(c, hipEventRecord(c->cev[1], st));
+  DRT_HIP(c, hipStreamSynchronize(st));
+  float ms_f = 0.f;
+  DRT_HIP(c, hipEventElapsedTime(&ms_f, c->cev[0], c->cev[1]));
+  *commit_ms = ms_f;
+  c->gmacro_shift = ms;
+  c->gmacro_dim[0] = mx; c->gmacro_dim[1] = my; c->gmacro_dim[2] = mz;
+  c->gmacro_words = (int)words;
+  memcpy(c->gdim, g.n, sizeof(c->gdim));
+  memcpy(c->gmin, g.bmin, sizeof(c->gmin));
+  memcpy(c->gmax, g.bmax, sizeof(c->gmax));
+  c->grid_cells.clear();
+  c->grid_cells_valid = false;
+  c->has_grid = true;
+  c->has_bvh = false;
+  return DRT_OK;
+}
+
+int drt_build_grid_device(drt_ctx* c, float m, int flags, drt_grid_build_info* info) {
+  if (!c) return DRT_E_INVALID;
+  if (flags & ~DRT_GRID_COMMIT_DEVICE) DRT_FAIL(c, DRT_E_INVALID, "bad flags %d", flags);
+  if (!c->has_scene) DRT_FAIL(c, DRT_E_STATE, "upload the scene before building its grid");
+  if (c->n_prims <= 0) DRT_FAIL(c, DRT_E_INVALID, "a scene without primitives has no grid to build");
+  const uint32_t n = (uint32_t)c->n_prims;
+  if (n > (1u << 26)) DRT_FAIL(c, DRT_E_UNSUPPORTED, "more than %u objects", 1u << 26);
+#if defined(DRT_GRID_RECS48) || defined(DRT_GRID_INDEXED)
+  const bool device_commit = false;  // (A/B layouts: the host commits)
+#else
+  const bool device_commit = (flags & DRT_GRID_COMMIT_DEVICE) != 0;
+#endif
+  c->has_bvh = c->has_grid = c->has_gv = c->has_ct = false;  // until the commit
+  c->grid_on_device = false;
+  DRT_HIP(c, hipSetDevice(c->device));
+  for (auto& e : c->bev)
+    if (!e) DRT_HIP(c, hipEventCreate(&e));
+  DRT_HIP(c, c->d_prims_raw.ensure(sizeof(drt_prim) * n));
+  DRT_HIP(c, c->d_gb_obj.fit(grid_object_scratch_bytes(n)));
+  DRT_HIP(c, c->d_gb_ranges.fit(24 * (size_t)n));
+  DRT_HIP(c, c->d_gb_status.ensure(sizeof(GridBuildStatus)));
+  DRT_HIP(c, c->h_gb_status.ensure(sizeof(GridBuildStatus)));
+  hipStream_t st = c->stream;
+  GridBuildStatus* ds = c->d_gb_status.as<GridBuildStatus>();
+  const GridBuildStatus* hs = (const GridBuildStatus*)c->h_gb_status.p;
+  auto read_status = [&]() -> hipError_t {
+    hipError_t e = hipMemcpyAsync(c->h_gb_status.p, ds, sizeof(GridBuildStatus), hipMemcpyDeviceToHost, st);
+    return e != hipSuccess ? e : hipStreamSynchronize(st);
+  };
+  DRT_HIP(c, hipEventRecord(c->bev[0], st));
+  if (!c->raw_resident) {
+    DRT_HIP(c, hipMemcpyAsync(c->d_prims_raw.p, c->prims_raw.data(), sizeof(drt_prim) * n, hipMemcpyHostToDevice, st));
+    c->raw_resident = true;
+  }
+  // stage 1: boxes and the world box; the cell counts on the host, with the host's pow
+  DRT_HIP(c, launch_grid_bounds(c->d_prims_raw.as<drt_prim>(), n, c->d_gb_obj.p, ds, st));
+  DRT_HIP(c, read_status());
+  if (hs->flags & kGridNonFinite) DRT_FAIL(c, DRT_E_UNSUPPORTED, "an object's box has a non-finite component");
+  GridDims g{};
+  for (int a = 0; a < 3; a++) {
+    g.bmin[a] = grid_unordered(hs->wbox[a]);
+    g.bmax[a] = grid_unordered(hs->wbox[3 + a]);
+  }
+  if (!grid_dims(g.bmin, g.bmax, (int)n, m, g.n)) DRT_FAIL(c, DRT_E_UNSUPPORTED, "the grid's cell counts are out of range");
+  const double cells_d = (double)g.n[0] * g.n[1] * g.n[2];
+  if (cells_d >= 2147483648.0) DRT_FAIL(c, DRT_E_UNSUPPORTED, "2^31 grid cells or more");
+  const size_t ncell = (size_t)g.n[0] * g.n[1] * g.n[2];
+  // stage 2: cell ranges and the number of references
+  DRT_HIP(c, launch_grid_ranges(n, g, c->d_gb_obj.p, c->d_gb_ranges.as<int32_t>(), ds, st));
+  DRT_HIP(c, read_status());
+  if (hs->n_refs >= 0x80000000ull) DRT_FAIL(c, DRT_E_UNSUPPORTED, "too many grid references");
+  const uint32_t n_refs = (uint32_t)hs->n_refs;
+  // stage 3: the lists, straight into the buffers the renderer reads
+  DRT_HIP(c, c->d_gb_refs.fit(grid_refs_scratch_bytes(n_refs)));
+  DRT_HIP(c, c->d_cell_start.ensure(4 * (ncell + 1)));
+  DRT_HIP(c, c->d_cell_objs.ensure(4 * std::max<size_t>(1, n_refs)));
+  DRT_HIP(c, launch_grid_lists(n, g, n_refs, c->d_gb_obj.p, c->d_gb_ranges.as<int32_t>(), c->d_gb_refs.p,
+                               c->d_cell_start.as<uint32_t>(), c->d_cell_objs.as<uint32_t>(), st));
+  DRT_HIP(c, hipEventRecord(c->bev[1], st));
+  DRT_HIP(c, hipStreamSynchronize(st));
+  drt_grid_build_info gi{};
+  memcpy(gi.dims, g.n, sizeof(gi.dims));
+  memcpy(gi.bmin, g.bmin, sizeof(gi.bmin));
+  memcpy(gi.bmax, g.bmax, sizeof(gi.bmax));
+  gi.n_cells = (int64_t)ncell;
+  gi.n_refs = n_refs;
+  gi.on_device = device_commit ? 1u : 0u;
+  float build_ms = 0.f, fetch_ms = 0.f;
+  DRT_HIP(c, hipEventElapsedTime(&build_ms, c->bev[0], c->bev[1]));
+  gi.build_ms = build_ms;
+  c->grid_info = gi;
+  if (device_commit) {
+    const int rc = commit_grid_device(c, g, n_refs, &gi.commit_ms);
+    if (rc) return rc;
+  } else {
+    const int frc = fetch_grid_device(c);
+    if (frc) return frc;
+    DRT_HIP(c, hipEventRecord(c->bev[2], st));
+    DRT_HIP(c, hipStreamSynchronize(st));
+    DRT_HIP(c, hipEventElapsedTime(&fetch_ms, c->bev[1], c->bev[2]));
+    gi.fetch_ms = fetch_ms;
+    const uint32_t* s32 = (const uint32_t*)c->h_gb_start.p;
+    std::vector<int64_t> cs(s32, s32 + ncell + 1);
+    const auto t0 = std::chrono::steady_clock::now();
+    const int rc = drt_upload_grid(c, g.n, g.bmin, g.bmax, cs.data(), (const int32_t*)c->h_gb_objs.p, n_refs);
+    if (rc) return rc;
+    gi.commit_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  }
+  c->grid_info = gi;
+  c->has_grid_info = true;
+  c->grid_on_device = true;  // d_cell_start / d_cell_objs hold the builder's lists (the host commit rewrote the same)
+  if (info) *info = gi;
+  return DRT_OK;
+}
+
+int drt_fetch_grid_device(drt_ctx* c, int64_t* cell_start, int32_t* cell_objs) {
+  if (!c) return DRT_E_INVALID;
+  if (!c->has_grid || !c->grid_on_device || !c->has_grid_info)
+    DRT_FAIL(c, DRT_E_STATE, "no device-built grid is resident");
+  DRT_HIP(c, hipSetDevice(c->device));
+  const int rc = fetch_grid_device(c);
+  if (rc) return rc;
+  const uint32_t* s32 = (const uint32_t*)c->h_gb_start.p;
+  if (cell_start)
+    for (int64_t i = 0; i <= c->grid_info.n_cells; i++) cell_start[i] = s32[i];
+  if (cell_objs && c->grid_info.n_refs) memcpy(cell_objs, c->h_gb_objs.p, 4 * (size_t)c->grid_info.n_refs);
+  return DRT_OK;
+}
+
+int drt_get_grid_build_info(const drt_ctx* c, drt_grid_build_info* info) {
+  if (!c || !info) return DRT_E_INVALID;
+  if (!c->has_grid_info) return DRT_E_STATE;
+  *info = c->grid_info;
   return DRT_OK;
 }
 
@@ -1292,6 +1517,8 @@ int drt_upload_grid_shadow_bvh(drt_ctx* c, const drt_bvh_node* nodes, uint32_t n
                                uint32_t n_obj) {
   if (!c || !nodes || n_nodes == 0) return DRT_E_INVALID;
   if (!c->has_grid) DRT_FAIL(c, DRT_E_STATE, "upload the grid before its shadow tree");
+  if (!c->grid_cells_valid)
+    DRT_FAIL(c, DRT_E_STATE, "the device-committed grid's cell ranges are on the device: drt_fetch_grid_device first");
   c->has_gv = c->has_ct = false;  // until this upload commits
   if ((int)n_obj != c->n_prims || (n_obj && !order)) DRT_FAIL(c, DRT_E_INVALID, "object_order must cover all %d objects", c->n_prims);
   const int cell = env_int("DRT_GRID_CELL_TREE", kCellTreeDefault);

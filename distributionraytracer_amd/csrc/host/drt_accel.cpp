@@ -291,16 +291,13 @@ void Grid::Build(std::vector<Object*>& objs) {  // grid.cpp:30-97
     gb.extend(bx[i]);
     addObject(objs[i]);
   }
-  gb.min.x = (float)((double)gb.min.x - kEps); gb.min.y = (float)((double)gb.min.y - kEps);
-  gb.min.z = (float)((double)gb.min.z - kEps);
-  gb.max.x = (float)((double)gb.max.x + kEps); gb.max.y = (float)((double)gb.max.y + kEps);
-  gb.max.z = (float)((double)gb.max.z + kEps);
-  bbox = gb;
-  const double wx = bbox.max.x - bbox.min.x, wy = bbox.max.y - bbox.min.y, wz = bbox.max.z - bbox.min.z;
-  const double s = std::pow((int)objs.size() / (wx * wy * wz), 0.3333333);
-  nx = (int)(m * wx * s + 1);
-  ny = (int)(m * wy * s + 1);
-  nz = (int)(m * wz * s + 1);
+  {
+    float mn[3] = {gb.min.x, gb.min.y, gb.min.z}, mx[3] = {gb.max.x, gb.max.y, gb.max.z};
+    int d[3];
+    (void)grid_dims(mn, mx, (int)objs.size(), m, d);
+    bbox = AABB(Vector(mn[0], mn[1], mn[2]), Vector(mx[0], mx[1], mx[2]));
+    nx = d[0]; ny = d[1]; nz = d[2];
+  }
   const int64_t cells = (int64_t)nx * ny * nz;
   // two passes (count, fill) over the same cell ranges -> CSR in insertion order
   auto range = [&](const AABB& ob, int r[6]) {
@@ -330,6 +327,25 @@ void Grid::Build(std::vector<Object*>& objs) {  // grid.cpp:30-97
         for (int ix = r[0]; ix <= r[3]; ix++) cell_objs[(size_t)fill[(size_t)(ix + nx * iy + nx * ny * iz)]++] = (int32_t)(base + i);
   }
   build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
+
+int Grid::Set(const std::vector<Object*>& objs, const int32_t dims[3], const float bmin[3], const float bmax[3],
+              const int64_t* cs, int64_t n_starts, const int32_t* co, int64_t n_refs) {
+  if (!dims || !bmin || !bmax || !cs || n_refs < 0 || (n_refs && !co)) return DRT_E_INVALID;
+  if (dims[0] <= 0 || dims[1] <= 0 || dims[2] <= 0) return DRT_E_INVALID;
+  const int64_t cells = (int64_t)dims[0] * dims[1] * dims[2];
+  if (n_starts != cells + 1 || cs[0] != 0 || cs[cells] != n_refs) return DRT_E_INVALID;
+  for (int64_t c = 0; c < cells; c++)
+    if (cs[c + 1] < cs[c]) return DRT_E_INVALID;
+  for (int64_t i = 0; i < n_refs; i++)
+    if (co[i] < 0 || (size_t)co[i] >= objs.size()) return DRT_E_INVALID;
+  objects = objs;
+  nx = dims[0]; ny = dims[1]; nz = dims[2];
+  bbox = AABB(Vector(bmin[0], bmin[1], bmin[2]), Vector(bmax[0], bmax[1], bmax[2]));
+  cell_start.assign(cs, cs + cells + 1);
+  cell_objs.assign(co, co + n_refs);
+  build_ms = 0.0;
+  return DRT_OK;
 }
 
 int Grid::upload(drt_ctx* ctx) const {

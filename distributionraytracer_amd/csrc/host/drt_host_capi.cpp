@@ -273,12 +273,26 @@ int drt_scene_set_bvh(drt_scene* s, const drt_bvh_node* nodes, uint32_t n_nodes,
   return DRT_OK;
 }
 
-// the scene description alone (upload_scene without its accelerator), then the tree from the device
-static int upload_for_device_build(drt_ctx* ctx, drt_scene* s) {
+int drt_scene_set_grid(drt_scene* s, const int32_t dims[3], const float bmin[3], const float bmax[3],
+                       const int64_t* cell_start, int64_t n_starts, const int32_t* cell_objs, int64_t n_refs) {
+  if (!s) return DRT_E_INVALID;
+  if (s->scene.GetAccelStruct() != GRID_ACC) return DRT_E_STATE;
+  Grid g;
+  const int rc = g.Set(s->scene.objectList(), dims, bmin, bmax, cell_start, n_starts, cell_objs, n_refs);
+  if (rc) return rc;
+  s->grid = std::move(g);
+  s->gv_bvh = BVH();
+  s->has_gv_bvh = false;
+  s->built = true;
+  return DRT_OK;
+}
+
+// the scene description alone (upload_scene without its accelerator), then the tree / grid from the device
+static int upload_for_device_build(drt_ctx* ctx, drt_scene* s, accelerator want = BVH_ACC) {
   if (!ctx || !s) return DRT_E_INVALID;
   if (!s->scene.GetCamera()) return DRT_E_STATE;
   if (s->scene.GetSkyBoxFlg() && !s->scene.SkyboxComplete()) return DRT_E_STATE;
-  if (s->scene.GetAccelStruct() != BVH_ACC) return DRT_E_STATE;
+  if (s->scene.GetAccelStruct() != want) return DRT_E_STATE;
   drt_scene_desc d;
   std::vector<drt_prim> prims;
   std::vector<drt_light> ls;
@@ -343,6 +357,27 @@ int drt_group_scene_upload_device_bvh(drt_group* g, drt_scene* s) {
     if (rc) return rc;
   }
   return DRT_OK;
+}
+
+int drt_scene_upload_device_grid(drt_ctx* ctx, drt_scene* s, int flags) {
+  if (flags & ~(DRT_GRID_COMMIT_DEVICE | DRT_GRID_NO_INSTALL)) return DRT_E_INVALID;
+  int rc = upload_for_device_build(ctx, s, GRID_ACC);
+  if (rc) return rc;
+  drt_grid_build_info info;
+  rc = drt_build_grid_device(ctx, s->grid.cellFactor(), flags & DRT_GRID_COMMIT_DEVICE, &info);
+  if (rc || (flags & DRT_GRID_NO_INSTALL)) return rc;
+  std::vector<int64_t> cs((size_t)info.n_cells + 1);
+  std::vector<int32_t> co((size_t)info.n_refs);
+  rc = drt_fetch_grid_device(ctx, cs.data(), co.data());
+  if (rc) return rc;
+  return drt_scene_set_grid(s, info.dims, info.bmin, info.bmax, cs.data(), (int64_t)cs.size(), co.data(), info.n_refs);
+}
+
+int drt_group_scene_upload_device_grid(drt_group* g, drt_scene* s) {
+  if (!g || !s) return DRT_E_INVALID;
+  int rc = drt_scene_upload_device_grid(drt_group_ctx(g, 0), s, 0);  // built once, on rank 0, and installed
+  for (int r = 1; !rc && r < drt_group_size(g); r++) rc = drt_scene_upload(drt_group_ctx(g, r), s);
+  return rc;
 }
 
 int drt_scene_load_skybox(drt_scene* s, const char* dir) {

@@ -246,6 +246,42 @@ typedef struct {
 int drt_get_bvh_commit_info(const drt_ctx* ctx, drt_bvh_commit_info* info);
 int drt_upload_grid(drt_ctx* ctx, const int32_t dims[3], const float bmin[3], const float bmax[3],
                     const int64_t* cell_start /* nx*ny*nz+1 */, const int32_t* cell_objs, int64_t n_refs);
+/* The uniform grid built on the device too (csrc/hip/drt_grid_build.hip): object boxes and the world box, the
+ * cell ranges, a reference expansion balanced by reference, a stable radix sort of the (cell, object) pairs and
+ * a scan over the cells, in hand-written HIP.  Unlike the device BVH, the result is exactly the host's:
+ * Grid::Build is a deterministic function of the object boxes, and dims, the grown box, cell_start and
+ * cell_objs come out bit for bit as drt_scene_build makes them (the cell counts are computed on the host with
+ * the same pow, from the world box alone).  Frames and every work count equal the host path's.
+ * The Grid scene's shadow tree is not built here: a device-built grid answers shadow queries by the Grid walk,
+ * which renders the same frame bit for bit at a lower frame rate, until drt_upload_grid_shadow_bvh adds a tree. */
+typedef struct {
+  int32_t dims[3];
+  float bmin[3], bmax[3]; /* the grown box                                                              */
+  int64_t n_cells, n_refs;
+  double build_ms;   /* device time from the first build kernel to the last, HIP events; the first build after
+                        a drt_upload_scene also stages the primitives on the device inside this time, and
+                        the two short host steps between the stages (cell counts, allocation) are inside  */
+  double fetch_ms;   /* device -> host copy of the lists (0 when they stayed on the device)               */
+  double commit_ms;  /* host clock around drt_upload_grid, or device time of the commit kernels           */
+  uint32_t on_device; /* 1: committed by the device kernels, 0: by the host (drt_upload_grid)             */
+  uint32_t reserved;
+} drt_grid_build_info;
+#define DRT_GRID_COMMIT_DEVICE 1
+/* After drt_upload_scene: build the grid of the resident primitives on the device with Grid::Build's cell
+ * factor m (2 in the reference).  flags = 0: the lists are fetched and committed through drt_upload_grid itself.
+ * DRT_GRID_COMMIT_DEVICE: the buffers drt_upload_grid fills (cell lists, inline records, tpos, macro-cell
+ * bitmap, scene-order primitives) are written by HIP kernels from the device-resident lists, byte for byte the
+ * same, and nothing but status words is copied back; drt_upload_grid_shadow_bvh then answers DRT_E_STATE until a
+ * drt_fetch_grid_device has brought the objects' cell ranges to the host.  DRT_E_STATE without a scene,
+ * DRT_E_INVALID for a scene without primitives or other flag bits, DRT_E_UNSUPPORTED for an object box with a
+ * non-finite component, 2^31 cells or references or more; DRT_E_OOM / DRT_E_HIP as elsewhere. */
+int drt_build_grid_device(drt_ctx* ctx, float m, int flags, drt_grid_build_info* info);
+/* The lists of the resident device-built grid: cell_start (n_cells + 1) and cell_objs (n_refs) as
+ * drt_upload_grid takes them, sizes from the info.  Either may be NULL.  DRT_E_STATE unless the resident grid
+ * came from drt_build_grid_device. */
+int drt_fetch_grid_device(drt_ctx* ctx, int64_t* cell_start, int32_t* cell_objs);
+/* The figures of the context's last drt_build_grid_device (DRT_E_STATE before one). */
+int drt_get_grid_build_info(const drt_ctx* ctx, drt_grid_build_info* info);
 /* Optional, after drt_upload_grid: a BVH of the same objects (the BVH::Build result, as drt_upload_bvh
  * takes it).  A triangle scene's wavefront shadow queries then walk a 4-ary tree collapsed from it with
  * widened boxes, and a hit counts only with a Grid cell certificate (the ray's point at the hit lies well

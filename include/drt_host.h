@@ -101,6 +101,22 @@ int drt_group_scene_upload_device_bvh(drt_group* g, drt_scene* s);
  * flag bits are DRT_E_INVALID.  The group form keeps the host commit. */
 enum { DRT_BVH_COMMIT_DEVICE = 1, DRT_BVH_NO_INSTALL = 2 };
 int drt_scene_upload_device_bvh_ex(drt_ctx* ctx, drt_scene* s, int flags);
+/* Install a caller's cell lists as a Grid scene's grid (the inverse of drt_scene_grid_export*): dims, box, CSR
+ * starts (n_starts = nx*ny*nz + 1) and cell objects (scene indices).  No geometry is computed.  DRT_E_INVALID,
+ * the scene unchanged, unless dims > 0, the starts run monotonically from 0 to n_refs, n_starts fits dims and
+ * every index is an object of the scene; DRT_E_STATE for a scene whose accelerator is not the Grid.  Marks the
+ * scene built, without a BVH for the shadow tree. */
+int drt_scene_set_grid(drt_scene* s, const int32_t dims[3], const float bmin[3], const float bmax[3],
+                       const int64_t* cell_start, int64_t n_starts, const int32_t* cell_objs, int64_t n_refs);
+/* drt_scene_upload of a Grid scene without the host build: the scene description, drt_build_grid_device
+ * (include/drt.h) with the scene's cell factor, then drt_fetch_grid_device and drt_scene_set_grid, so the host
+ * scene holds the grid the device walks.  DRT_GRID_COMMIT_DEVICE (include/drt.h) commits on the device;
+ * DRT_GRID_NO_INSTALL skips the fetch and the install (the host scene is then not marked built by this call).
+ * No shadow tree is uploaded: shadow queries take the Grid walk.  The group form builds once, on rank 0,
+ * installs, and uploads to the other ranks by the host path. */
+enum { DRT_GRID_NO_INSTALL = 2 };
+int drt_scene_upload_device_grid(drt_ctx* ctx, drt_scene* s, int flags);
+int drt_group_scene_upload_device_grid(drt_group* g, drt_scene* s);
 /* The scene's current camera frame to a context / every device of a group (drt_set_camera): the
  * per-frame camera of the interactive renderer (main.cpp:530-533) with the scene resident. */
 int drt_scene_upload_camera(drt_ctx* ctx, const drt_scene* s);

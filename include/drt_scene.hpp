@@ -379,6 +379,27 @@ class BVH {
   std::vector<int> order_;     // permutation being sorted (positions into boxes_/cents_)
 };
 
+// Grid::Build's box growth and cell counts (grid.cpp:47-67) of the objects' world box: the box grows by
+// EPSILON in double, then nx, ny, nz = (int)(m * width * cbrt-ish(n / volume) + 1) with the host's pow.  Shared
+// by Grid::Build and the device builder's entry point (drt_build_grid_device), so the two cannot drift.
+// False when a count is not in [1, 2^31) (the casts are then meaningless).
+inline bool grid_dims(float bmin[3], float bmax[3], int n_objects, float m, int dims[3]) {
+  constexpr double eps = 0.001;  // macros.h:1 (a double)
+  for (int a = 0; a < 3; a++) {
+    bmin[a] = (float)((double)bmin[a] - eps);
+    bmax[a] = (float)((double)bmax[a] + eps);
+  }
+  const double wx = bmax[0] - bmin[0], wy = bmax[1] - bmin[1], wz = bmax[2] - bmin[2];
+  const double s = std::pow(n_objects / (wx * wy * wz), 0.3333333);
+  const double d[3] = {m * wx * s + 1, m * wy * s + 1, m * wz * s + 1};
+  bool ok = true;
+  for (int a = 0; a < 3; a++) {
+    dims[a] = (int)d[a];
+    ok = ok && d[a] >= 1.0 && d[a] < 2147483648.0;
+  }
+  return ok;
+}
+
 class Grid {
  public:
   Grid() = default;
@@ -387,6 +408,13 @@ class Grid {
   Object* getObject(unsigned index) const { return index < objects.size() ? objects[index] : nullptr; }
   void setAABB(const AABB& b) { bbox = b; }
   void Build(std::vector<Object*>& objs);  // grid.cpp:30-97 (appends objs to the object list)
+  // A caller's cell lists over `objs` in place of Build's (drt_scene_set_grid; e.g. the device-built grid of
+  // drt_build_grid_device): dims, box and CSR as drt_scene_grid_export gives them.  No geometry is computed.
+  // DRT_E_INVALID, and the grid left as it was, unless dims > 0, cell_start has nx*ny*nz + 1 monotone entries
+  // from 0 to n_refs and every cell object is a position in objs.
+  int Set(const std::vector<Object*>& objs, const int32_t dims[3], const float bmin[3], const float bmax[3],
+          const int64_t* cell_start, int64_t n_starts, const int32_t* cell_objs, int64_t n_refs);
+  float cellFactor() const { return m; }  // Build's m
   // Scalar queries on the CPU (grid.cpp:247-306 closest, :309-358 shadow: range |d|, and a
   // ray that misses the grid box counts as shadowed)
   bool Traverse(Ray& ray, Object** hitobject, HitRecord& hitRec) const;
