@@ -4,8 +4,8 @@
 //   bvh_prim_bounds   one lane per primitive: its box (bit-identical to the host's GetBoundingBox(),
 //                     include/drt_scene.hpp, drt_scene.cpp:18-33) and the scene's centroid bounds
 //   bvh_morton        63-bit Morton keys of the centroids, and the histogram of all eight key bytes
-//   bvh_sort_*        stable LSD radix sort of (key, scene index), 8-bit digits, passes whose digit is the
-//                     same for every key skipped
+//   bvh_sort_*        stable LSD radix sort of (key, scene index), 8-bit digits (the tile of
+//                     drt_scan_sort.hpp), passes whose digit is the same for every key skipped
 //   bvh_radix_tree    one lane per internal node of the binary radix tree over the sorted keys
 //   bvh_refit         one lane per sorted position climbs the parent links: boxes, depths, inner counts
 //   bvh_emit          renumbers into the drt_upload_bvh format (children adjacent, index > own index)
@@ -15,7 +15,8 @@
 // No lane waits for another lane, wave or workgroup: the stages are ordered by kernel boundaries on one
 // stream, the only cross-workgroup traffic inside a kernel is atomic adds / mins / maxes whose results no
 // one polls, and bvh_refit's arrival counter lets the first arrival leave.  Workgroup barriers
-// (__syncthreads) order the LDS staging of one workgroup.
+// (__syncthreads) order the LDS staging of one workgroup.  The scans, the wave reduction and the sort tile are
+// drt_scan_sort.hpp's, shared with drt_bvh_commit.hip and drt_grid_build.hip.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -23,15 +24,15 @@
 #include "../../../include/drt.h"
 #include "drt_bvh_build.hpp"
 #include "drt_prim_device.hpp"
+#include "drt_scan_sort.hpp"
 
 namespace drt {
 
 namespace {
 
-constexpr int kThreads = 256;  // every kernel's workgroup: four waves of 64
-constexpr uint32_t kNone = 0xFFFFFFFFu;
-constexpr int kKpt = kBvhSortTile / kThreads;  // keys per thread of the sort
-static_assert(kKpt * kThreads == kBvhSortTile && kKpt == 8, "the tile is 4 waves x 8 rounds x 64 lanes");
+// keys one sort workgroup ranks and stages in LDS: 16 KB of keys + 8 KB of payloads + 6 KB of counters, of
+// the 64 KB a workgroup may hold
+constexpr int kBvhSortTile = kTile;
 
 // node data of the refit, 8 words per node id: box min, box max, depth, inner count
 constexpr int kNodeWords = 8;
@@ -62,60 +63,34 @@ struct Arena {
   uint32_t* ndata;     // kNodeWords per node id
 };
 
-__host__ __device__ inline size_t align256(size_t x) { return (x + 255u) & ~(size_t)255u; }
-
 Arena carve(void* scratch, uint32_t n, size_t* total) {
-  const size_t nwg = (n + kBvhSortTile - 1) / kBvhSortTile;
+  const size_t nwg = div_up(n, kBvhSortTile);
   const size_t ids = 2 * (size_t)n;  // 2n - 1 used
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    char* p = (char*)scratch + off;
-    off += align256(bytes);
-    return (void*)p;
-  };
+  ScratchSlicer s{scratch};
   Arena a;
-  a.pbox = (float4*)take(sizeof(float4) * 2 * n);
-  a.key[0] = (uint64_t*)take(sizeof(uint64_t) * n);
-  a.key[1] = (uint64_t*)take(sizeof(uint64_t) * n);
-  a.pay[0] = (uint32_t*)take(sizeof(uint32_t) * n);
-  a.pay[1] = (uint32_t*)take(sizeof(uint32_t) * n);
-  a.table = (uint32_t*)take(sizeof(uint32_t) * 256 * nwg);
-  a.ghist = (uint32_t*)take(sizeof(uint32_t) * 8 * 256);
-  a.plan = (SortPlan*)take(sizeof(SortPlan));
-  a.cbounds = (uint32_t*)take(sizeof(uint32_t) * 8);
-  a.left = (uint32_t*)take(sizeof(uint32_t) * n);
-  a.right = (uint32_t*)take(sizeof(uint32_t) * n);
-  a.first = (uint32_t*)take(sizeof(uint32_t) * n);
-  a.last = (uint32_t*)take(sizeof(uint32_t) * n);
-  a.parent = (uint32_t*)take(sizeof(uint32_t) * ids);
-  a.arrive = (uint32_t*)take(sizeof(uint32_t) * n);
-  a.ndata = (uint32_t*)take(sizeof(uint32_t) * kNodeWords * ids);
-  if (total) *total = off;
+  a.pbox = s.take<float4>(2 * (size_t)n);
+  a.key[0] = s.take<uint64_t>(n);
+  a.key[1] = s.take<uint64_t>(n);
+  a.pay[0] = s.take<uint32_t>(n);
+  a.pay[1] = s.take<uint32_t>(n);
+  a.table = s.take<uint32_t>(256 * nwg);
+  a.ghist = s.take<uint32_t>(8 * 256);
+  a.plan = s.take<SortPlan>(1);
+  a.cbounds = s.take<uint32_t>(8);
+  a.left = s.take<uint32_t>(n);
+  a.right = s.take<uint32_t>(n);
+  a.first = s.take<uint32_t>(n);
+  a.last = s.take<uint32_t>(n);
+  a.parent = s.take<uint32_t>(ids);
+  a.arrive = s.take<uint32_t>(n);
+  a.ndata = s.take<uint32_t>(kNodeWords * ids);
+  if (total) *total = s.used;
   return a;
 }
 
 // ---- small helpers ---------------------------------------------------------------------------------
 __device__ inline float smin(float a, float b) { return (b < a) ? b : a; }  // std::min, as drt_accel.cpp
 __device__ inline float smax(float a, float b) { return (a < b) ? b : a; }  // std::max
-
-// Exclusive scan of one value per thread over the 256 threads of the workgroup (wave scans by cross-lane
-// shifts, the four wave totals through LDS); every thread gets the workgroup's total.
-__device__ inline uint32_t block_scan_excl(uint32_t v, uint32_t* wave_tot /* LDS, 4 words */, uint32_t& total) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  uint32_t inc = v;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const uint32_t up = __shfl_up(inc, d, 64);
-    if (lane >= d) inc += up;
-  }
-  __syncthreads();  // the previous use of wave_tot is over
-  if (lane == 63) wave_tot[w] = inc;
-  __syncthreads();
-  const uint32_t t0 = wave_tot[0], t1 = wave_tot[1], t2 = wave_tot[2], t3 = wave_tot[3];
-  total = t0 + t1 + t2 + t3;
-  const uint32_t before = (w > 0 ? t0 : 0u) + (w > 1 ? t1 : 0u) + (w > 2 ? t2 : 0u);
-  return before + inc - v;
-}
 
 // ---- stage 0: clear ---------------------------------------------------------------------------------
 __global__ __launch_bounds__(kThreads) void bvh_clear(Arena A, uint32_t n, uint32_t* info) {
@@ -149,12 +124,7 @@ __global__ __launch_bounds__(kThreads) void bvh_prim_bounds(const drt_prim* __re
     const float c = centroid1(lo[a], hi[a]);
     const bool use = valid && finite(c);
     uint32_t mn = use ? ordered(c) : 0xFFFFFFFFu, mx = use ? ordered(c) : 0u;
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-      const uint32_t omn = __shfl_xor(mn, d, 64), omx = __shfl_xor(mx, d, 64);
-      mn = omn < mn ? omn : mn;
-      mx = omx > mx ? omx : mx;
-    }
+    wave_min_max(mn, mx);
     if ((threadIdx.x & 63) == 0 && mn <= mx) {
       atomicMin(&A.cbounds[a], mn);
       atomicMax(&A.cbounds[3 + a], mx);
@@ -206,7 +176,7 @@ __global__ __launch_bounds__(kThreads) void bvh_morton(uint32_t n, Arena A) {
     if (h[k]) atomicAdd(&A.ghist[k], h[k]);
 }
 
-// ---- stage 3: stable LSD radix sort --------------------------------------------------------------
+// ---- stage 3: stable LSD radix sort (why it is stable: radix_scatter_tile, drt_scan_sort.hpp) ------
 // One workgroup: which passes run, which buffer each reads, and each pass's digit bases.
 __global__ __launch_bounds__(kThreads) void bvh_sort_plan(uint32_t n, Arena A) {
   __shared__ uint32_t wave_tot[4];
@@ -218,7 +188,7 @@ __global__ __launch_bounds__(kThreads) void bvh_sort_plan(uint32_t n, Arena A) {
     const uint32_t v = A.ghist[p * 256 + t];
     if (v == n) skip[p] = 1u;  // one digit holds every key
     uint32_t total;
-    A.plan->gbase[p][t] = block_scan_excl(v, wave_tot, total);
+    A.plan->gbase[p][t] = block_scan_excl<uint32_t>(v, wave_tot, total);
   }
   __syncthreads();
   if (t == 0) {
@@ -232,114 +202,23 @@ __global__ __launch_bounds__(kThreads) void bvh_sort_plan(uint32_t n, Arena A) {
   }
 }
 
-__device__ inline uint32_t digit_of(uint64_t key, int pass) { return (uint32_t)((key >> (8 * pass)) & 255u); }
-
 // per-workgroup digit histogram of the tile -> table[digit * n_wg + wg]
 __global__ __launch_bounds__(kThreads) void bvh_sort_count(uint32_t n, uint32_t n_wg, int pass, Arena A) {
   if (A.plan->skip[pass]) return;
-  __shared__ uint32_t h[256];
-  const int t = threadIdx.x;
-  h[t] = 0u;
-  __syncthreads();
-  const uint64_t* __restrict__ src = A.key[A.plan->src[pass]];
-  const uint32_t base = blockIdx.x * (uint32_t)kBvhSortTile;
-#pragma unroll
-  for (int j = 0; j < kKpt; j++) {
-    const uint32_t i = base + j * kThreads + t;
-    if (i < n) atomicAdd(&h[digit_of(src[i], pass)], 1u);
-  }
-  __syncthreads();
-  A.table[(size_t)t * n_wg + blockIdx.x] = h[t];
+  radix_count_tile<uint64_t>(A.key[A.plan->src[pass]], n, n_wg, pass, A.table);
 }
 
 // one workgroup per digit: exclusive scan of the digit's row of n_wg counts, offset by the digit's base
 __global__ __launch_bounds__(kThreads) void bvh_sort_scan(uint32_t n_wg, int pass, Arena A) {
   if (A.plan->skip[pass]) return;
-  __shared__ uint32_t wave_tot[4];
-  uint32_t* row = A.table + (size_t)blockIdx.x * n_wg;
-  uint32_t carry = A.plan->gbase[pass][blockIdx.x];
-  for (uint32_t c = 0; c < n_wg; c += kThreads) {
-    const uint32_t k = c + threadIdx.x;
-    const uint32_t v = k < n_wg ? row[k] : 0u;
-    uint32_t total;
-    const uint32_t ex = block_scan_excl(v, wave_tot, total);
-    if (k < n_wg) row[k] = carry + ex;
-    carry += total;
-  }
+  (void)block_scan_array<uint32_t>(A.table + (size_t)blockIdx.x * n_wg, n_wg, A.plan->gbase[pass][blockIdx.x]);
 }
 
-// Rank the tile's keys by digit, stage them in LDS in digit order, write each digit's run contiguously.
-// Wave w owns positions [512 w, 512 w + 512) of the tile and takes them 64 at a time, so (wave, round,
-// lane) is ascending position and ranking in that order keeps equal digits in input order (stable).
+// the tile's keys and payloads, ranked by digit, from the pass's source buffer to the other one
 __global__ __launch_bounds__(kThreads) void bvh_sort_scatter(uint32_t n, uint32_t n_wg, int pass, Arena A) {
   if (A.plan->skip[pass]) return;
-  __shared__ uint64_t skey[kBvhSortTile];
-  __shared__ uint32_t spay[kBvhSortTile];
-  __shared__ uint32_t wcnt[4][256];  // per wave and digit: keys ranked so far, then the waves' exclusive prefix
-  __shared__ uint32_t dstart[256];   // first staged position of each digit
-  __shared__ uint32_t gbase[256];    // first global position of this tile's run of each digit
-  __shared__ uint32_t wave_tot[4];
-  const int t = threadIdx.x, lane = t & 63, w = t >> 6;
   const uint32_t sel = A.plan->src[pass];
-  const uint64_t* __restrict__ ksrc = A.key[sel];
-  const uint32_t* __restrict__ psrc = A.pay[sel];
-  uint64_t* __restrict__ kdst = A.key[sel ^ 1u];
-  uint32_t* __restrict__ pdst = A.pay[sel ^ 1u];
-  const uint32_t base = blockIdx.x * (uint32_t)kBvhSortTile;
-#pragma unroll
-  for (int k = 0; k < 4; k++) wcnt[k][t] = 0u;
-  __syncthreads();
-  uint64_t key[kKpt];
-  uint32_t pay[kKpt], off[kKpt];
-  const uint64_t below = (1ull << lane) - 1ull;
-#pragma unroll
-  for (int r = 0; r < kKpt; r++) {
-    const uint32_t i = base + w * (64 * kKpt) + r * 64 + lane;
-    const bool valid = i < n;
-    key[r] = valid ? ksrc[i] : ~0ull;
-    pay[r] = valid ? psrc[i] : 0u;
-    const uint32_t d = digit_of(key[r], pass);
-    uint64_t mask = __ballot(valid);  // the lanes of this wave holding the same digit as this lane
-#pragma unroll
-    for (int b = 0; b < 8; b++) {
-      const bool bit = (d >> b) & 1u;
-      const uint64_t m = __ballot(bit);
-      mask &= bit ? m : ~m;
-    }
-    const uint32_t prior = wcnt[w][d];
-    __syncthreads();  // every lane has read the counter before its digit's first lane advances it
-    const uint32_t rank = (uint32_t)__popcll(mask & below);
-    if (valid && rank == 0u) wcnt[w][d] = prior + (uint32_t)__popcll(mask);
-    __syncthreads();
-    off[r] = prior + rank;
-  }
-  {  // thread t = digit t: the waves' counts -> exclusive prefix over waves; digit starts; global bases
-    const uint32_t c0 = wcnt[0][t], c1 = wcnt[1][t], c2 = wcnt[2][t], c3 = wcnt[3][t];
-    uint32_t total;
-    const uint32_t ex = block_scan_excl(c0 + c1 + c2 + c3, wave_tot, total);
-    wcnt[0][t] = 0u; wcnt[1][t] = c0; wcnt[2][t] = c0 + c1; wcnt[3][t] = c0 + c1 + c2;
-    dstart[t] = ex;
-    gbase[t] = A.table[(size_t)t * n_wg + blockIdx.x];
-  }
-  __syncthreads();
-#pragma unroll
-  for (int r = 0; r < kKpt; r++) {
-    const uint32_t i = base + w * (64 * kKpt) + r * 64 + lane;
-    const uint32_t d = digit_of(key[r], pass);
-    const uint32_t pos = dstart[d] + wcnt[w][d] + off[r];
-    if (i < n && pos < (uint32_t)kBvhSortTile) { skey[pos] = key[r]; spay[pos] = pay[r]; }
-  }
-  __syncthreads();
-  const uint32_t count = n - base < (uint32_t)kBvhSortTile ? n - base : (uint32_t)kBvhSortTile;
-#pragma unroll
-  for (int j = 0; j < kKpt; j++) {
-    const uint32_t i = j * kThreads + t;
-    if (i >= count) continue;
-    const uint64_t k = skey[i];
-    const uint32_t d = digit_of(k, pass);
-    const uint32_t g = gbase[d] + (i - dstart[d]);
-    if (g < n) { kdst[g] = k; pdst[g] = spay[i]; }
-  }
+  radix_scatter_tile<uint64_t>(A.key[sel], A.pay[sel], A.key[sel ^ 1u], A.pay[sel ^ 1u], n, n_wg, pass, A.table);
 }
 
 // ---- stage 4: binary radix tree ------------------------------------------------------------------
@@ -513,33 +392,25 @@ size_t bvh_build_scratch_bytes(uint32_t n_prims) {
   return total;
 }
 
-#define BVH_LAUNCH(kernel, grid, ...)                                      \
-  do {                                                                     \
-    hipLaunchKernelGGL(kernel, dim3(grid), dim3(kThreads), 0, st, __VA_ARGS__); \
-    const hipError_t _e = hipGetLastError();                               \
-    if (_e != hipSuccess) return _e;                                       \
-  } while (0)
-
 hipError_t launch_bvh_build(const drt_prim* d_prims, uint32_t n, void* d_scratch, drt_bvh_node* d_nodes,
                             uint32_t* d_order, uint32_t* d_info, hipStream_t st) {
   if (!d_prims || !d_scratch || !d_nodes || !d_order || !d_info || n == 0 || n > (1u << 26)) return hipErrorInvalidValue;
   const Arena A = carve(d_scratch, n, nullptr);
-  const uint32_t per_prim = (n + kThreads - 1) / kThreads;
-  const uint32_t per_id = (2 * n - 1 + kThreads - 1) / kThreads;
-  const uint32_t n_wg = (n + kBvhSortTile - 1) / kBvhSortTile;
+  const uint32_t per_prim = div_up(n, kThreads), per_id = div_up(2 * n - 1, kThreads);
+  const uint32_t n_wg = div_up(n, kBvhSortTile);
   const uint32_t clear_grid = per_id > 8u ? per_id : 8u;  // also covers the 8 x 256 histogram
-  BVH_LAUNCH(bvh_clear, clear_grid, A, n, d_info);
-  BVH_LAUNCH(bvh_prim_bounds, per_prim, d_prims, n, A);
-  BVH_LAUNCH(bvh_morton, per_prim, n, A);
-  BVH_LAUNCH(bvh_sort_plan, 1, n, A);
+  DRT_LAUNCH(bvh_clear, clear_grid, A, n, d_info);
+  DRT_LAUNCH(bvh_prim_bounds, per_prim, d_prims, n, A);
+  DRT_LAUNCH(bvh_morton, per_prim, n, A);
+  DRT_LAUNCH(bvh_sort_plan, 1, n, A);
   for (int pass = 0; pass < 8; pass++) {
-    BVH_LAUNCH(bvh_sort_count, n_wg, n, n_wg, pass, A);
-    BVH_LAUNCH(bvh_sort_scan, 256, n_wg, pass, A);
-    BVH_LAUNCH(bvh_sort_scatter, n_wg, n, n_wg, pass, A);
+    DRT_LAUNCH(bvh_sort_count, n_wg, n, n_wg, pass, A);
+    DRT_LAUNCH(bvh_sort_scan, 256, n_wg, pass, A);
+    DRT_LAUNCH(bvh_sort_scatter, n_wg, n, n_wg, pass, A);
   }
-  if (n > 1) BVH_LAUNCH(bvh_radix_tree, (n - 1 + kThreads - 1) / kThreads, n, A);
-  BVH_LAUNCH(bvh_refit, per_prim, n, A);
-  BVH_LAUNCH(bvh_emit, per_id, n, A, d_nodes, d_order, d_info);
+  if (n > 1) DRT_LAUNCH(bvh_radix_tree, div_up(n - 1, kThreads), n, A);
+  DRT_LAUNCH(bvh_refit, per_prim, n, A);
+  DRT_LAUNCH(bvh_emit, per_id, n, A, d_nodes, d_order, d_info);
   return hipSuccess;
 }
 

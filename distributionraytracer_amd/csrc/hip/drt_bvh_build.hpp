@@ -9,10 +9,6 @@
 
 namespace drt {
 
-// keys one sort workgroup (256 threads x 8) ranks and stages in LDS: 16 KB of keys + 8 KB of payloads,
-// + 6 KB of counters, of the 64 KB a workgroup may hold
-constexpr int kBvhSortTile = 2048;
-
 // bytes of device scratch a build of n_prims primitives needs
 size_t bvh_build_scratch_bytes(uint32_t n_prims);
 

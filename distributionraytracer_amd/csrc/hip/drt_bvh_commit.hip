@@ -13,6 +13,7 @@
 //                       parent's line ("paired": the inner child of larger surface of a head)?  The lane walks
 //                       up its chain of larger-surface links; per-workgroup head counts
 //   commit_scan         one workgroup: exclusive scan of the per-workgroup counts, the total
+//                       (block_scan_array of drt_scan_sort.hpp, whose flag and wave scans the others use)
 //   commit_place        a head's line = the exclusive prefix sum of head flags in node-slot order; the head
 //                       places itself at 2 * line and its larger inner child at 2 * line + 1
 //   commit_records      one lane per record slot: the 64-B record (or zeros for a padding slot), four 16-B
@@ -35,14 +36,13 @@
 
 #include "drt_bvh_commit.hpp"
 #include "drt_prim_device.hpp"
+#include "drt_scan_sort.hpp"
 
 namespace drt {
 
 namespace {
 
-constexpr int kThreads = 256;
-constexpr uint32_t kNone = 0xFFFFFFFFu;
-constexpr int kMaxLevels = 128;          // level counters (the host launches far fewer levels)
+constexpr int kMaxLevels = 128;         // level counters (the host launches far fewer levels)
 constexpr uint32_t kLevelGridMax = 1024;  // workgroups of a frontier launch (grid-stride beyond)
 
 struct Arena {
@@ -58,29 +58,22 @@ struct Arena {
   uint32_t* level_cnt;  // kMaxLevels frontier sizes
 };
 
-inline size_t align256(size_t x) { return (x + 255u) & ~(size_t)255u; }
-
 Arena carve(void* scratch, uint32_t n, size_t* total) {
   const size_t nodes = 2 * (size_t)n, inner = n;  // 2n - 1 and n - 1 used
-  size_t off = 0;
-  auto take = [&](size_t words) {
-    char* p = (char*)scratch + off;
-    off += align256(sizeof(uint32_t) * words);
-    return (uint32_t*)p;
-  };
+  ScratchSlicer s{scratch};
   Arena a;
-  a.rank_slot = take(inner);
-  a.head = take(nodes);
-  a.pos = take(nodes);
-  a.slot_node = take(2 * inner);
-  a.wmark = take(nodes);
-  a.widx = take(nodes);
-  a.wlist = take(inner);
-  a.frontier[0] = take(inner);
-  a.frontier[1] = take(inner);
-  a.wg_counts = take((nodes + kThreads - 1) / kThreads + 1);
-  a.level_cnt = take(kMaxLevels);
-  if (total) *total = off;
+  a.rank_slot = s.take<uint32_t>(inner);
+  a.head = s.take<uint32_t>(nodes);
+  a.pos = s.take<uint32_t>(nodes);
+  a.slot_node = s.take<uint32_t>(2 * inner);
+  a.wmark = s.take<uint32_t>(nodes);
+  a.widx = s.take<uint32_t>(nodes);
+  a.wlist = s.take<uint32_t>(inner);
+  a.frontier[0] = s.take<uint32_t>(inner);
+  a.frontier[1] = s.take<uint32_t>(inner);
+  a.wg_counts = s.take<uint32_t>((nodes + kThreads - 1) / kThreads + 1);
+  a.level_cnt = s.take<uint32_t>(kMaxLevels);
+  if (total) *total = s.used;
   return a;
 }
 
@@ -103,31 +96,6 @@ __device__ inline uint32_t larger_child(const drt_bvh_node* __restrict__ nodes, 
 
 __device__ inline uint32_t node_desc(const drt_bvh_node& nd, const uint32_t* __restrict__ inner_index, uint32_t i) {
   return nd.leaf ? leaf_desc(nd.index, nd.n_objs) : inner_index[i];
-}
-
-// Exclusive prefix count of one flag per thread over the workgroup: a ballot per wave, the four wave totals
-// through LDS (one exchange); every thread gets the workgroup's total.
-__device__ inline uint32_t block_flag_scan(bool f, uint32_t* wave_tot /* LDS, 4 words */, uint32_t& total) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const uint64_t m = __ballot(f);
-  if (lane == 0) wave_tot[w] = (uint32_t)__popcll(m);
-  __syncthreads();
-  const uint32_t t0 = wave_tot[0], t1 = wave_tot[1], t2 = wave_tot[2], t3 = wave_tot[3];
-  total = t0 + t1 + t2 + t3;
-  const uint32_t before = (w > 0 ? t0 : 0u) + (w > 1 ? t1 : 0u) + (w > 2 ? t2 : 0u);
-  return before + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
-}
-
-// inclusive scan of one value per lane across the wave (cross-lane shifts)
-__device__ inline uint32_t wave_scan_incl(uint32_t v) {
-  const int lane = threadIdx.x & 63;
-  uint32_t inc = v;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const uint32_t up = __shfl_up(inc, d, 64);
-    if (lane >= d) inc += up;
-  }
-  return inc;
 }
 
 // ---- stage 1: binary records and their placement ---------------------------------------------------
@@ -184,22 +152,8 @@ __global__ __launch_bounds__(kThreads) void commit_heads(const drt_bvh_node* __r
 
 // One workgroup: counts[0 .. n) -> their exclusive scan in place, the total to *total_out.
 __global__ __launch_bounds__(kThreads) void commit_scan(uint32_t* counts, uint32_t n, uint32_t* total_out) {
-  __shared__ uint32_t wave_tot[4];
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  uint32_t carry = 0u;
-  for (uint32_t c = 0; c < n; c += kThreads) {
-    const uint32_t k = c + threadIdx.x;
-    const uint32_t v = k < n ? counts[k] : 0u;
-    const uint32_t inc = wave_scan_incl(v);
-    __syncthreads();  // the previous round's reads of wave_tot are over
-    if (lane == 63) wave_tot[w] = inc;
-    __syncthreads();
-    const uint32_t t0 = wave_tot[0], t1 = wave_tot[1], t2 = wave_tot[2], t3 = wave_tot[3];
-    const uint32_t before = (w > 0 ? t0 : 0u) + (w > 1 ? t1 : 0u) + (w > 2 ? t2 : 0u);
-    if (k < n) counts[k] = carry + before + inc - v;
-    carry += t0 + t1 + t2 + t3;
-  }
-  if (threadIdx.x == 0) *total_out = carry;
+  const uint32_t total = block_scan_array<uint32_t>(counts, n, 0u);
+  if (threadIdx.x == 0) *total_out = total;
 }
 
 __global__ __launch_bounds__(kThreads) void commit_place(const drt_bvh_node* __restrict__ nodes, uint32_t n_nodes,
@@ -543,13 +497,6 @@ size_t bvh_commit_scratch_bytes(uint32_t n_prims) {
   return total;
 }
 
-#define COMMIT_LAUNCH(kernel, grid, ...)                                        \
-  do {                                                                          \
-    hipLaunchKernelGGL(kernel, dim3(grid), dim3(kThreads), 0, st, __VA_ARGS__); \
-    const hipError_t _e = hipGetLastError();                                    \
-    if (_e != hipSuccess) return _e;                                            \
-  } while (0)
-
 hipError_t launch_bvh_commit(const BvhCommitArgs& a, hipStream_t st) {
   if (!a.nodes || !a.order || !a.prims_raw || !a.scratch || !a.recs || !a.wide_recs || !a.leaf_boxes || !a.prims ||
       !a.status || a.n_prims == 0 || a.n_prims > (1u << 26) || a.n_nodes == 0 || !(a.n_nodes & 1u) ||
@@ -561,15 +508,15 @@ hipError_t launch_bvh_commit(const BvhCommitArgs& a, hipStream_t st) {
   const uint32_t per_inner = (n_inner + kThreads - 1) / kThreads;
   const uint32_t per_both = ((n_nodes > n ? n_nodes : n) + kThreads - 1) / kThreads;
   const int wide = a.wide && n_inner > 0;
-  COMMIT_LAUNCH(commit_index, per_node, a.nodes, n_nodes, A, a.status);
+  DRT_LAUNCH(commit_index, per_node, a.nodes, n_nodes, A, a.status);
   if (n_inner > 0) {
-    COMMIT_LAUNCH(commit_heads, per_node, a.nodes, n_nodes, A);
-    COMMIT_LAUNCH(commit_scan, 1, A.wg_counts, per_node, &a.status->n_lines);
-    COMMIT_LAUNCH(commit_place, per_node, a.nodes, n_nodes, A);
-    COMMIT_LAUNCH(commit_records, (2 * n_inner + kThreads - 1) / kThreads, a.nodes, n_nodes, A, a.status,
+    DRT_LAUNCH(commit_heads, per_node, a.nodes, n_nodes, A);
+    DRT_LAUNCH(commit_scan, 1, A.wg_counts, per_node, &a.status->n_lines);
+    DRT_LAUNCH(commit_place, per_node, a.nodes, n_nodes, A);
+    DRT_LAUNCH(commit_records, (2 * n_inner + kThreads - 1) / kThreads, a.nodes, n_nodes, A, a.status,
                   (float4*)a.recs);
   }
-  COMMIT_LAUNCH(commit_leaf_prims, per_both, a.nodes, n_nodes, a.order, (const float4*)a.prims_raw, n,
+  DRT_LAUNCH(commit_leaf_prims, per_both, a.nodes, n_nodes, a.order, (const float4*)a.prims_raw, n,
                 a.default_material, wide, (float4*)a.leaf_boxes, (float4*)a.prims);
   if (!wide) return hipSuccess;
   // wide roots sit above the leaves, so there are at most depth - 1 levels of them
@@ -578,11 +525,11 @@ hipError_t launch_bvh_commit(const BvhCommitArgs& a, hipStream_t st) {
   if (levels > kMaxLevels - 1) levels = kMaxLevels - 1;
   const uint32_t level_grid = per_inner < kLevelGridMax ? per_inner : kLevelGridMax;
   for (int level = 0; level < levels; level++)
-    COMMIT_LAUNCH(commit_wide_level, level_grid, a.nodes, n_nodes, A, level, a.status);
-  COMMIT_LAUNCH(commit_wide_count, per_node, n_nodes, A);
-  COMMIT_LAUNCH(commit_scan, 1, A.wg_counts, per_node, &a.status->n_wide);
-  COMMIT_LAUNCH(commit_wide_place, per_node, n_nodes, A);
-  COMMIT_LAUNCH(commit_wide_write, per_inner, a.nodes, n_nodes, A, a.status, (uint4*)a.wide_recs);
+    DRT_LAUNCH(commit_wide_level, level_grid, a.nodes, n_nodes, A, level, a.status);
+  DRT_LAUNCH(commit_wide_count, per_node, n_nodes, A);
+  DRT_LAUNCH(commit_scan, 1, A.wg_counts, per_node, &a.status->n_wide);
+  DRT_LAUNCH(commit_wide_place, per_node, n_nodes, A);
+  DRT_LAUNCH(commit_wide_write, per_inner, a.nodes, n_nodes, A, a.status, (uint4*)a.wide_recs);
   return hipSuccess;
 }
 

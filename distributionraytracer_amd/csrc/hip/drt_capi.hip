@@ -1015,6 +1015,22 @@ static int commit_bvh_device(drt_ctx* c, uint32_t n, uint32_t n_nodes, uint32_t 
   return DRT_OK;
 }
 
+// What the device builders (BVH and grid) share: the events around a build and its fetch, created on first use ...
+static int ensure_build_events(drt_ctx* c) {
+  for (auto& e : c->bev)
+    if (!e) DRT_HIP(c, hipEventCreate(&e));
+  return DRT_OK;
+}
+
+// ... and the scene-order drt_prim records in d_prims_raw (sized by the caller), copied once per uploaded scene
+static int raw_prims_to_device(drt_ctx* c, hipStream_t st) {
+  if (c->raw_resident) return DRT_OK;
+  DRT_HIP(c, hipMemcpyAsync(c->d_prims_raw.p, c->prims_raw.data(), sizeof(drt_prim) * (size_t)c->n_prims,
+                            hipMemcpyHostToDevice, st));
+  c->raw_resident = true;
+  return DRT_OK;
+}
+
 // drt_build_bvh_device and drt_build_bvh_device_commit: the build, then the host or the device commit
 static int build_bvh_device(drt_ctx* c, drt_bvh_node* nodes_out, uint32_t* order_out, drt_bvh_build_info* info,
                             bool device_commit) {
@@ -1025,8 +1041,7 @@ static int build_bvh_device(drt_ctx* c, drt_bvh_node* nodes_out, uint32_t* order
   if (n > kFirstMask) DRT_FAIL(c, DRT_E_UNSUPPORTED, "more than %u objects", kFirstMask);
   c->has_bvh = c->has_grid = c->has_gv = c->has_ct = false;  // until the commit
   DRT_HIP(c, hipSetDevice(c->device));
-  for (auto& e : c->bev)
-    if (!e) DRT_HIP(c, hipEventCreate(&e));
+  if (const int rc = ensure_build_events(c)) return rc;
   const size_t max_nodes = 2 * (size_t)n - 1;
   DRT_HIP(c, c->d_prims_raw.ensure(sizeof(drt_prim) * n));
   // The device commit needs DRT_NODE_LAYOUT=1, DRT_WIDE_ORDER=2 and 4-ary records: otherwise the host commits
@@ -1045,10 +1060,7 @@ static int build_bvh_device(drt_ctx* c, drt_bvh_node* nodes_out, uint32_t* order
   DRT_HIP(c, c->h_build_info.ensure(sizeof(uint32_t) * 4));
   hipStream_t st = c->stream;
   DRT_HIP(c, hipEventRecord(c->bev[0], st));
-  if (!c->raw_resident) {
-    DRT_HIP(c, hipMemcpyAsync(c->d_prims_raw.p, c->prims_raw.data(), sizeof(drt_prim) * n, hipMemcpyHostToDevice, st));
-    c->raw_resident = true;
-  }
+  if (const int rc = raw_prims_to_device(c, st)) return rc;
   DRT_HIP(c, launch_bvh_build(c->d_prims_raw.as<drt_prim>(), n, c->d_build.p, c->d_build_nodes.as<drt_bvh_node>(),
                               c->d_build_order.as<uint32_t>(), c->d_build_info.as<uint32_t>(), st));
   DRT_HIP(c, hipEventRecord(c->bev[1], st));
@@ -1412,8 +1424,7 @@ int drt_build_grid_device(drt_ctx* c, float m, int flags, drt_grid_build_info* i
   c->has_bvh = c->has_grid = c->has_gv = c->has_ct = false;  // until the commit
   c->grid_on_device = false;
   DRT_HIP(c, hipSetDevice(c->device));
-  for (auto& e : c->bev)
-    if (!e) DRT_HIP(c, hipEventCreate(&e));
+  if (const int rc = ensure_build_events(c)) return rc;
   DRT_HIP(c, c->d_prims_raw.ensure(sizeof(drt_prim) * n));
   DRT_HIP(c, c->d_gb_obj.fit(grid_object_scratch_bytes(n)));
   DRT_HIP(c, c->d_gb_ranges.fit(24 * (size_t)n));
@@ -1427,10 +1438,7 @@ int drt_build_grid_device(drt_ctx* c, float m, int flags, drt_grid_build_info* i
     return e != hipSuccess ? e : hipStreamSynchronize(st);
   };
   DRT_HIP(c, hipEventRecord(c->bev[0], st));
-  if (!c->raw_resident) {
-    DRT_HIP(c, hipMemcpyAsync(c->d_prims_raw.p, c->prims_raw.data(), sizeof(drt_prim) * n, hipMemcpyHostToDevice, st));
-    c->raw_resident = true;
-  }
+  if (const int rc = raw_prims_to_device(c, st)) return rc;
   // stage 1: boxes and the world box; the cell counts on the host, with the host's pow
   DRT_HIP(c, launch_grid_bounds(c->d_prims_raw.as<drt_prim>(), n, c->d_gb_obj.p, ds, st));
   DRT_HIP(c, read_status());

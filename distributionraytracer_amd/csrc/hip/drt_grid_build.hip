@@ -3,7 +3,7 @@
 // object boxes, the same float arithmetic for the cell ranges, each cell's objects in insertion order.
 //
 //   grid_bounds        one lane per object: its box (prim_bounds, as the BVH builder) and the world box — min /
-//                      max across the wave by cross-lane shuffles, then one ordered-uint atomic per wave and axis
+//                      max across the wave (wave_min_max), then one ordered-uint atomic per wave and axis
 //   (host)             the grown box and nx, ny, nz with glibc's pow (grid_dims, include/drt_scene.hpp)
 //   grid_ranges        one lane per object: its six cell indices (24 B) and its 64-bit cell count; the
 //                      workgroup's exclusive scan of the counts and its total
@@ -14,10 +14,10 @@
 //                      tile mark their first slot in LDS, a max-scan over the slots gives every slot its object,
 //                      and each lane decodes its slot into (object, ix, iy, iz): a (cell, object) pair in object
 //                      order, and the cell's count
-//   grid_sort_*        stable LSD radix sort of the pairs by cell, 8-bit digits, only the passes n_cells needs;
-//                      count / scan / scatter as bvh_sort_* (rank in LDS, each digit's run written
-//                      contiguously).  Stable, and an object lists a cell once: every cell's run comes out in
-//                      ascending object index, Grid::Build's insertion order
+//   grid_sort_*        stable LSD radix sort of the pairs by cell, 8-bit digits, only the passes n_cells needs:
+//                      the tile of drt_scan_sort.hpp that bvh_sort_* runs on 64-bit keys (rank in LDS, each
+//                      digit's run written contiguously).  Stable, and an object lists a cell once: every
+//                      cell's run comes out in ascending object index, Grid::Build's insertion order
 //   grid_scan_*        device-wide exclusive scan (tile sums, scan of the sums, write): the cell counts ->
 //                      cell_start, every cell written; a pass's digit table -> its scatter bases; the commit's
 //                      padded cell counts -> tpos
@@ -34,17 +34,15 @@
 
 #include "drt_grid_build.hpp"
 #include "drt_prim_device.hpp"
+#include "drt_scan_sort.hpp"
 
 namespace drt {
 
 namespace {
 
-constexpr int kThreads = 256;  // every kernel's workgroup: four waves of 64
-constexpr int kPer = kGridTile / kThreads;
-static_assert(kPer * kThreads == kGridTile && kPer == 8, "the tile is 4 waves x 8 rounds x 64 lanes");
-
-__host__ __device__ inline size_t align256(size_t x) { return (x + 255u) & ~(size_t)255u; }
-inline uint32_t div_up(uint64_t a, uint32_t b) { return (uint32_t)((a + b - 1) / b); }
+// reference slots one expansion workgroup owns, pairs one sort workgroup ranks (8 KB of keys + 8 KB of values
+// + 6 KB of counters in LDS), values one scan workgroup scans
+constexpr int kGridTile = kTile;
 
 struct ObjArena {
   float4* pbox;        // 2 per object, scene order: (min, 0), (max, 0)
@@ -61,37 +59,27 @@ struct RefArena {
 };
 
 ObjArena carve_obj(void* scratch, uint32_t n, size_t* total) {
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    char* p = (char*)scratch + off;
-    off += align256(bytes);
-    return (void*)p;
-  };
+  ScratchSlicer s{scratch};
   ObjArena a;
-  a.pbox = (float4*)take(sizeof(float4) * 2 * n);
-  a.local = (uint64_t*)take(sizeof(uint64_t) * n);
-  a.blocks = (uint64_t*)take(sizeof(uint64_t) * (div_up(n, kThreads) + 1));
-  a.off = (uint32_t*)take(sizeof(uint32_t) * ((size_t)n + 1));
-  if (total) *total = off;
+  a.pbox = s.take<float4>(2 * (size_t)n);
+  a.local = s.take<uint64_t>(n);
+  a.blocks = s.take<uint64_t>(div_up(n, kThreads) + 1);
+  a.off = s.take<uint32_t>((size_t)n + 1);
+  if (total) *total = s.used;
   return a;
 }
 
 RefArena carve_refs(void* scratch, uint32_t n_refs, size_t* total) {
   const size_t r = n_refs ? n_refs : 1u, n_wg = div_up(r, kGridTile);
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    char* p = (char*)scratch + off;
-    off += align256(bytes);
-    return (uint32_t*)p;
-  };
+  ScratchSlicer s{scratch};
   RefArena a;
-  a.key[0] = take(4 * r);
-  a.key[1] = take(4 * r);
-  a.val[0] = take(4 * r);
-  a.val[1] = take(4 * r);
-  a.table = take(4 * (256 * n_wg + 1));
-  a.sums = take(4 * ((size_t)(1u << 20) + 2));  // a scan of up to 2^31 values has up to 2^20 tiles
-  if (total) *total = off;
+  a.key[0] = s.take<uint32_t>(r);
+  a.key[1] = s.take<uint32_t>(r);
+  a.val[0] = s.take<uint32_t>(r);
+  a.val[1] = s.take<uint32_t>(r);
+  a.table = s.take<uint32_t>(256 * n_wg + 1);
+  a.sums = s.take<uint32_t>((size_t)(1u << 20) + 2);  // a scan of up to 2^31 values has up to 2^20 tiles
+  if (total) *total = s.used;
   return a;
 }
 
@@ -100,45 +88,6 @@ inline int sort_passes(uint64_t n_cells) {
   int p = 0;
   while (p < 4 && ((n_cells - 1) >> (8 * p)) != 0) p++;
   return p;
-}
-
-// ---- workgroup scans --------------------------------------------------------------------------------
-// Exclusive scan of one value per thread over the 256 threads (wave scans by cross-lane shifts, the four
-// wave totals through LDS); every thread gets the workgroup's total.
-template <class T>
-__device__ inline T block_scan_excl(T v, T* wave_tot /* LDS, 4 */, T& total) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  T inc = v;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const T up = __shfl_up(inc, d, 64);
-    if (lane >= d) inc += up;
-  }
-  __syncthreads();  // the previous use of wave_tot is over
-  if (lane == 63) wave_tot[w] = inc;
-  __syncthreads();
-  const T t0 = wave_tot[0], t1 = wave_tot[1], t2 = wave_tot[2], t3 = wave_tot[3];
-  total = t0 + t1 + t2 + t3;
-  const T before = (w > 0 ? t0 : (T)0) + (w > 1 ? t1 : (T)0) + (w > 2 ? t2 : (T)0);
-  return before + inc - v;
-}
-
-// the same with max in place of +: the largest value of the threads before this one (floor if none)
-__device__ inline uint32_t block_max_excl(uint32_t v, uint32_t floor, uint32_t* wave_tot /* LDS, 4 */) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  uint32_t inc = v;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const uint32_t up = __shfl_up(inc, d, 64);
-    if (lane >= d) inc = up > inc ? up : inc;
-  }
-  uint32_t ex = __shfl_up(inc, 1, 64);
-  if (lane == 0) ex = floor;
-  __syncthreads();
-  if (lane == 63) wave_tot[w] = inc;
-  __syncthreads();
-  for (int k = 0; k < w; k++) ex = wave_tot[k] > ex ? wave_tot[k] : ex;
-  return ex;
 }
 
 // ---- stage 1: object boxes, world box ---------------------------------------------------------------
@@ -165,12 +114,7 @@ __global__ __launch_bounds__(kThreads) void grid_bounds(const drt_prim* __restri
 #pragma unroll
   for (int a = 0; a < 3; a++) {
     uint32_t mn = valid ? ordered(lo[a]) : 0xFFFFFFFFu, mx = valid ? ordered(hi[a]) : 0u;
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-      const uint32_t omn = __shfl_xor(mn, d, 64), omx = __shfl_xor(mx, d, 64);
-      mn = omn < mn ? omn : mn;
-      mx = omx > mx ? omx : mx;
-    }
+    wave_min_max(mn, mx);
     if ((threadIdx.x & 63) == 0) {
       atomicMin(&status->wbox[a], mn);
       atomicMax(&status->wbox[3 + a], mx);
@@ -215,17 +159,8 @@ __global__ __launch_bounds__(kThreads) void grid_ranges(uint32_t n, GridDims g, 
 
 // one workgroup: the workgroup totals -> their exclusive scan in place, the grand total
 __global__ __launch_bounds__(kThreads) void grid_scan_blocks(uint32_t n_blocks, ObjArena A, GridBuildStatus* status) {
-  __shared__ uint64_t wave_tot[4];
-  uint64_t carry = 0ull;
-  for (uint32_t c = 0; c < n_blocks; c += kThreads) {
-    const uint32_t k = c + threadIdx.x;
-    const uint64_t v = k < n_blocks ? A.blocks[k] : 0ull;
-    uint64_t total;
-    const uint64_t ex = block_scan_excl<uint64_t>(v, wave_tot, total);
-    if (k < n_blocks) A.blocks[k] = carry + ex;
-    carry += total;
-  }
-  if (threadIdx.x == 0) status->n_refs = carry;
+  const uint64_t total = block_scan_array<uint64_t>(A.blocks, n_blocks, 0ull);
+  if (threadIdx.x == 0) status->n_refs = total;
 }
 
 // (the words are meaningful once the host has seen n_refs < 2^31)
@@ -339,19 +274,10 @@ __global__ __launch_bounds__(kThreads) void grid_scan_reduce(const uint32_t* __r
 
 // one workgroup: the tile sums -> their exclusive scan in place, the total after them and, if asked, in *total_out
 __global__ __launch_bounds__(kThreads) void grid_scan_sums(uint32_t* sums, uint32_t n_tiles, uint32_t* total_out) {
-  __shared__ uint32_t wave_tot[4];
-  uint32_t carry = 0u;
-  for (uint32_t c = 0; c < n_tiles; c += kThreads) {
-    const uint32_t k = c + threadIdx.x;
-    const uint32_t v = k < n_tiles ? sums[k] : 0u;
-    uint32_t total;
-    const uint32_t ex = block_scan_excl<uint32_t>(v, wave_tot, total);
-    if (k < n_tiles) sums[k] = carry + ex;
-    carry += total;
-  }
+  const uint32_t total = block_scan_array<uint32_t>(sums, n_tiles, 0u);
   if (threadIdx.x == 0) {
-    sums[n_tiles] = carry;
-    if (total_out) *total_out = carry;
+    sums[n_tiles] = total;
+    if (total_out) *total_out = total;
   }
 }
 
@@ -378,110 +304,28 @@ __global__ __launch_bounds__(kThreads) void grid_scan_write(const uint32_t* in, 
   if (blockIdx.x == n_tiles - 1u && threadIdx.x == 0) out[n] = scan_word<MODE>(in, n, sums[n_tiles]);
 }
 
-#define GRID_LAUNCH(kernel, grid, ...)                                          \
-  do {                                                                          \
-    hipLaunchKernelGGL(kernel, dim3(grid), dim3(kThreads), 0, st, __VA_ARGS__); \
-    const hipError_t _e = hipGetLastError();                                    \
-    if (_e != hipSuccess) return _e;                                            \
-  } while (0)
-
 template <int MODE>
 hipError_t device_scan(const uint32_t* in, uint32_t n, uint32_t* sums, uint32_t* out, uint32_t* total_out, hipStream_t st) {
   const uint32_t n_tiles = div_up(n ? n : 1u, kGridTile);
-  GRID_LAUNCH(grid_scan_reduce<MODE>, n_tiles, in, n, sums);
-  GRID_LAUNCH(grid_scan_sums, 1, sums, n_tiles, total_out);
-  GRID_LAUNCH(grid_scan_write<MODE>, n_tiles, in, n, sums, n_tiles, out);
+  DRT_LAUNCH(grid_scan_reduce<MODE>, n_tiles, in, n, sums);
+  DRT_LAUNCH(grid_scan_sums, 1, sums, n_tiles, total_out);
+  DRT_LAUNCH(grid_scan_write<MODE>, n_tiles, in, n, sums, n_tiles, out);
   return hipSuccess;
 }
 
-// ---- stable LSD radix sort of (cell, object) --------------------------------------------------------
-__device__ inline uint32_t digit_of(uint32_t key, int pass) { return (key >> (8 * pass)) & 255u; }
-
+// ---- stable LSD radix sort of (cell, object): the tile of drt_scan_sort.hpp ------------------------
 // per-workgroup digit histogram of the tile -> table[digit * n_wg + wg]
 __global__ __launch_bounds__(kThreads) void grid_sort_count(const uint32_t* __restrict__ src, uint32_t n, uint32_t n_wg,
                                                             int pass, uint32_t* __restrict__ table) {
-  __shared__ uint32_t h[256];
-  const int t = threadIdx.x;
-  h[t] = 0u;
-  __syncthreads();
-  const uint32_t base = blockIdx.x * (uint32_t)kGridTile;
-#pragma unroll
-  for (int j = 0; j < kPer; j++) {
-    const uint32_t i = base + j * kThreads + t;
-    if (i < n) atomicAdd(&h[digit_of(src[i], pass)], 1u);
-  }
-  __syncthreads();
-  table[(size_t)t * n_wg + blockIdx.x] = h[t];
+  radix_count_tile<uint32_t>(src, n, n_wg, pass, table);
 }
 
-// Rank the tile's pairs by digit, stage them in LDS in digit order, write each digit's run contiguously.
-// Wave w owns positions [512 w, 512 w + 512) of the tile and takes them 64 at a time, so (wave, round, lane)
-// is ascending position and ranking in that order keeps equal digits in input order (stable).  table holds
-// the exclusive scan of the digit-major counts: the first global position of this tile's run of each digit.
+// table holds the exclusive scan of the digit-major counts; stable (radix_scatter_tile), so a cell's run
+// keeps the expansion's object order
 __global__ __launch_bounds__(kThreads) void grid_sort_scatter(const uint32_t* __restrict__ ksrc, const uint32_t* __restrict__ vsrc,
                                                               uint32_t* __restrict__ kdst, uint32_t* __restrict__ vdst, uint32_t n,
                                                               uint32_t n_wg, int pass, const uint32_t* __restrict__ table) {
-  __shared__ uint32_t skey[kGridTile];
-  __shared__ uint32_t sval[kGridTile];
-  __shared__ uint32_t wcnt[4][256];  // per wave and digit: pairs ranked so far, then the waves' exclusive prefix
-  __shared__ uint32_t dstart[256];   // first staged position of each digit
-  __shared__ uint32_t gbase[256];    // first global position of this tile's run of each digit
-  __shared__ uint32_t wave_tot[4];
-  const int t = threadIdx.x, lane = t & 63, w = t >> 6;
-  const uint32_t base = blockIdx.x * (uint32_t)kGridTile;
-#pragma unroll
-  for (int k = 0; k < 4; k++) wcnt[k][t] = 0u;
-  __syncthreads();
-  uint32_t key[kPer], val[kPer], off[kPer];
-  const uint64_t below = (1ull << lane) - 1ull;
-#pragma unroll
-  for (int r = 0; r < kPer; r++) {
-    const uint32_t i = base + w * (64 * kPer) + r * 64 + lane;
-    const bool valid = i < n;
-    key[r] = valid ? ksrc[i] : 0xFFFFFFFFu;
-    val[r] = valid ? vsrc[i] : 0u;
-    const uint32_t d = digit_of(key[r], pass);
-    uint64_t mask = __ballot(valid);  // the lanes of this wave holding the same digit as this lane
-#pragma unroll
-    for (int b = 0; b < 8; b++) {
-      const bool bit = (d >> b) & 1u;
-      const uint64_t m = __ballot(bit);
-      mask &= bit ? m : ~m;
-    }
-    const uint32_t prior = wcnt[w][d];
-    __syncthreads();  // every lane has read the counter before its digit's first lane advances it
-    const uint32_t rank = (uint32_t)__popcll(mask & below);
-    if (valid && rank == 0u) wcnt[w][d] = prior + (uint32_t)__popcll(mask);
-    __syncthreads();
-    off[r] = prior + rank;
-  }
-  {  // thread t = digit t: the waves' counts -> exclusive prefix over waves; digit starts; global bases
-    const uint32_t c0 = wcnt[0][t], c1 = wcnt[1][t], c2 = wcnt[2][t], c3 = wcnt[3][t];
-    uint32_t total;
-    const uint32_t ex = block_scan_excl<uint32_t>(c0 + c1 + c2 + c3, wave_tot, total);
-    wcnt[0][t] = 0u; wcnt[1][t] = c0; wcnt[2][t] = c0 + c1; wcnt[3][t] = c0 + c1 + c2;
-    dstart[t] = ex;
-    gbase[t] = table[(size_t)t * n_wg + blockIdx.x];
-  }
-  __syncthreads();
-#pragma unroll
-  for (int r = 0; r < kPer; r++) {
-    const uint32_t i = base + w * (64 * kPer) + r * 64 + lane;
-    const uint32_t d = digit_of(key[r], pass);
-    const uint32_t pos = dstart[d] + wcnt[w][d] + off[r];
-    if (i < n && pos < (uint32_t)kGridTile) { skey[pos] = key[r]; sval[pos] = val[r]; }
-  }
-  __syncthreads();
-  const uint32_t count = n - base < (uint32_t)kGridTile ? n - base : (uint32_t)kGridTile;
-#pragma unroll
-  for (int j = 0; j < kPer; j++) {
-    const uint32_t i = j * kThreads + t;
-    if (i >= count) continue;
-    const uint32_t k = skey[i];
-    const uint32_t d = digit_of(k, pass);
-    const uint32_t gpos = gbase[d] + (i - dstart[d]);
-    if (gpos < n) { kdst[gpos] = k; vdst[gpos] = sval[i]; }
-  }
+  radix_scatter_tile<uint32_t>(ksrc, vsrc, kdst, vdst, n, n_wg, pass, table);
 }
 
 __global__ __launch_bounds__(kThreads) void grid_copy(const uint32_t* __restrict__ src, uint32_t n, uint32_t* __restrict__ dst) {
@@ -553,8 +397,8 @@ hipError_t launch_grid_bounds(const drt_prim* d_prims, uint32_t n, void* obj_scr
                               hipStream_t st) {
   if (!d_prims || !obj_scratch || !status || n == 0 || n > (1u << 26)) return hipErrorInvalidValue;
   const ObjArena A = carve_obj(obj_scratch, n, nullptr);
-  GRID_LAUNCH(grid_clear_status, 1, status);
-  GRID_LAUNCH(grid_bounds, div_up(n, kThreads), d_prims, n, A, status);
+  DRT_LAUNCH(grid_clear_status, 1, status);
+  DRT_LAUNCH(grid_bounds, div_up(n, kThreads), d_prims, n, A, status);
   return hipSuccess;
 }
 
@@ -563,9 +407,9 @@ hipError_t launch_grid_ranges(uint32_t n, const GridDims& g, void* obj_scratch, 
   if (!obj_scratch || !ranges || !status || n == 0 || n > (1u << 26)) return hipErrorInvalidValue;
   const ObjArena A = carve_obj(obj_scratch, n, nullptr);
   const uint32_t n_blocks = div_up(n, kThreads);
-  GRID_LAUNCH(grid_ranges, n_blocks, n, g, A, ranges);
-  GRID_LAUNCH(grid_scan_blocks, 1, n_blocks, A, status);
-  GRID_LAUNCH(grid_offsets, div_up((uint64_t)n + 1, kThreads), n, A, status);
+  DRT_LAUNCH(grid_ranges, n_blocks, n, g, A, ranges);
+  DRT_LAUNCH(grid_scan_blocks, 1, n_blocks, A, status);
+  DRT_LAUNCH(grid_offsets, div_up((uint64_t)n + 1, kThreads), n, A, status);
   return hipSuccess;
 }
 
@@ -581,16 +425,16 @@ hipError_t launch_grid_lists(uint32_t n, const GridDims& g, uint32_t n_refs, con
   if (e != hipSuccess) return e;
   if (n_refs > 0) {
     const uint32_t n_wg = div_up(n_refs, kGridTile);
-    GRID_LAUNCH(grid_expand, n_wg, n, n_refs, g, A, ranges, R.key[0], R.val[0], cell_start);
+    DRT_LAUNCH(grid_expand, n_wg, n, n_refs, g, A, ranges, R.key[0], R.val[0], cell_start);
     const int passes = sort_passes(n_cells);
     for (int pass = 0; pass < passes; pass++) {
       const int s = pass & 1;
-      GRID_LAUNCH(grid_sort_count, n_wg, R.key[s], n_refs, n_wg, pass, R.table);
+      DRT_LAUNCH(grid_sort_count, n_wg, R.key[s], n_refs, n_wg, pass, R.table);
       e = device_scan<kCounts>(R.table, 256u * n_wg, R.sums, R.table, nullptr, st);
       if (e != hipSuccess) return e;
-      GRID_LAUNCH(grid_sort_scatter, n_wg, R.key[s], R.val[s], R.key[s ^ 1], R.val[s ^ 1], n_refs, n_wg, pass, R.table);
+      DRT_LAUNCH(grid_sort_scatter, n_wg, R.key[s], R.val[s], R.key[s ^ 1], R.val[s ^ 1], n_refs, n_wg, pass, R.table);
     }
-    GRID_LAUNCH(grid_copy, div_up(n_refs, kThreads), R.val[passes & 1], n_refs, cell_objs);
+    DRT_LAUNCH(grid_copy, div_up(n_refs, kThreads), R.val[passes & 1], n_refs, cell_objs);
   }
   return device_scan<kCounts>(cell_start, (uint32_t)n_cells, R.sums, cell_start, nullptr, st);
 }
@@ -609,10 +453,10 @@ hipError_t launch_grid_commit(const GridCommitArgs& a, hipStream_t st) {
       (a.tris ? !a.tpos : !a.recs) || n_cells == 0 || n_cells >= (1ull << 31))
     return hipErrorInvalidValue;
   const RefArena R = carve_refs(a.refs_scratch, a.n_refs, nullptr);
-  GRID_LAUNCH(grid_commit_prims, div_up(a.n_prims, kThreads), (const float4*)a.prims_raw, a.n_prims, a.default_material,
+  DRT_LAUNCH(grid_commit_prims, div_up(a.n_prims, kThreads), (const float4*)a.prims_raw, a.n_prims, a.default_material,
               (float4*)a.prims);
   if (a.n_refs > 0)
-    GRID_LAUNCH(grid_commit_refs, div_up(a.n_refs, kThreads), a, (const uint32_t*)R.key[sort_passes(n_cells) & 1]);
+    DRT_LAUNCH(grid_commit_refs, div_up(a.n_refs, kThreads), a, (const uint32_t*)R.key[sort_passes(n_cells) & 1]);
   return hipSuccess;
 }
 

@@ -10,10 +10,6 @@
 
 namespace drt {
 
-// reference slots one expansion workgroup owns, keys one sort workgroup ranks, values one scan workgroup
-// scans (256 threads x 8): 8 KB of keys + 8 KB of values + 6 KB of counters in LDS
-constexpr int kGridTile = 2048;
-
 enum : uint32_t { kGridNonFinite = 1u };  // GridBuildStatus::flags: an object box has a non-finite component
 
 // The words the host reads back between the stages (64 B).

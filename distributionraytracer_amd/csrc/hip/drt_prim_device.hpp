@@ -1,6 +1,8 @@
 // drt_prim_device.hpp — what the device builders (drt_bvh_build.hip, drt_grid_build.hip) and the device
 // commits (drt_bvh_commit.hip, drt_grid_build.hip) derive from a scene-order drt_prim: its box, bit-identical
-// to the host's GetBoundingBox(), and its 48-B primitive record, as pack_prim (drt_capi.hip) packs it.
+// to the host's GetBoundingBox(), the order-preserving words its bounds are reduced in, and its 48-B primitive
+// record, as pack_prim (drt_capi.hip) packs it.  What they share that does not know a primitive (scans, the
+// sort tile, launch and scratch plumbing) is in drt_scan_sort.hpp.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -5,7 +5,10 @@ the device walk against the host walk, frames and work counts against the host p
 Scene sizes are the smallest at which a stage can go wrong: 1, 2, 65 (one over a wave), one more than the
 reference-slot tile, 20 000 (more cells than the macro-cell bitmap holds, a partial last tile everywhere); one
 axis of a single cell; long runs of empty cells; mixed primitives on the 48-B records; two triangles that span
-the whole box, so one object's references cover many workgroups and cells hold odd counts.
+the whole box, so one object's references cover many workgroups and cells hold odd counts; 70 000 triangles,
+whose grid has more than 256 scan tiles of cells, so the one-workgroup scan of the tile sums
+(block_scan_array, csrc/hip/drt_scan_sort.hpp, which every builder's chunked scan runs) takes a second
+256-wide round with a carry.
 """
 import numpy as np
 import pytest
@@ -16,16 +19,18 @@ pytestmark = pytest.mark.gpu
 
 T = 2048  # reference slots per workgroup (kGridTile)
 SIZES = {"soup1": 1, "soup2": 2, "soup65": 65, "soupT1": T + 1, "soup20k": 20000}
-CASES = list(SIZES) + ["flat", "clusters", "mixed", "floor"]
+BIG = "soup70k"  # more than T * 256 cells
+CASES = list(SIZES) + ["flat", "clusters", "mixed", "floor", BIG]
 FRAMES = ["soup20k", "mixed", "floor"]
 
 
 def grid_scene(drt, name):
-    if name != "floor":
+    if name not in ("floor", BIG):
         return make_scene(drt, name, accel="grid")
     import bench
 
-    tris = bench.synthetic_triangles(2000, 3)[:2000]
+    n = 70000 if name == BIG else 2000
+    tris = bench.synthetic_triangles(n, 3)[:n]
     v = tris.reshape(-1, 3, 3)
     lo, hi = v.min((0, 1)).astype(np.float64), v.max((0, 1)).astype(np.float64)
     floor = np.array([[lo[0], lo[1], lo[2], hi[0], lo[1], lo[2], hi[0], hi[1], hi[2]],
@@ -36,7 +41,7 @@ def grid_scene(drt, name):
     s.set_spp(16)
     s.add_light_quad((4, 3, 2), (1, 1, 1), (4, 2, 2), (3, 3, 2), 16)
     s.add_material((1, 0.9, 0.7), 0.5, (1, 1, 1), 0.5, 30.0827, 0, 1)
-    s.add_triangles(np.concatenate([tris, floor]))
+    s.add_triangles(np.concatenate([tris, floor]) if name == "floor" else tris)
     eye = (lo + hi) / 2 + (hi - lo + 1.0) * (1.1, 0.9, 0.7)
     s.set_camera(eye, (lo + hi) / 2, (0, 0, 1), 45.0, 0.01, 64, 48, 0.0, 1.0)
     return s, None, eye, lo, hi
@@ -96,6 +101,7 @@ def test_lists_and_walks_equal_the_host_grid(name, commit, drt, renderer, host):
         shift += 1
     print(name, commit, "dims", got["dims"], "n_refs", len(got["cell_objs"]), "macro shift", shift)
     same_grid(got, host(name)[1])
+    assert name != BIG or info["n_cells"] > T * 256  # or the case no longer reaches the scan's second round
     assert info["dims"] == got["dims"] and info["n_refs"] == len(got["cell_objs"])
     assert info["n_cells"] == len(got["cell_start"]) - 1 and info["on_device"] == (commit == "device")
     assert (bits(info["bmin"]) == bits(got["bmin"])).all() and (bits(info["bmax"]) == bits(got["bmax"])).all()
