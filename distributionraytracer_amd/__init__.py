@@ -285,23 +285,29 @@ class Renderer:
         A Grid scene with build="device" gets its grid from HIP kernels too (drt_build_grid_device): exactly
         the host's cell lists, bit for bit, committed by drt_upload_grid (commit="host") or by kernels
         (commit="device").  No shadow tree is built for it: shadow queries take the Grid walk, which renders
-        the same frame at a lower rate."""
-        if build not in ("host", "device"):
-            raise ValueError(f"build must be 'host' or 'device', not {build!r}")
+        the same frame at a lower rate.
+        build="ploc" (BVH scenes only): as build="device" with the PLOC builder (drt_build_bvh_device_ex,
+        csrc/hip/drt_bvh_ploc.hip) in place of the LBVH: more kernel rounds to build, a tree of lower
+        surface-area cost (README.md, Use); commit and install as with build="device"."""
+        if build not in ("host", "device", "ploc"):
+            raise ValueError(f"build must be 'host', 'device' or 'ploc', not {build!r}")
         if commit not in ("host", "device"):
             raise ValueError(f"commit must be 'host' or 'device', not {commit!r}")
         if build == "host" and (commit == "device" or not install):
-            raise ValueError("commit='device' and install=False need build='device'")
+            raise ValueError("commit='device' and install=False need build='device' or 'ploc'")
+        if build == "ploc" and scene.info().accel == ACCEL["grid"]:
+            raise ValueError("build='ploc' is a BVH builder: a Grid scene has one device builder, build='device'")
         if build == "host":
             check(_lib.load().drt_scene_upload(self.h, scene.h), self.h, "drt_scene_upload")
         elif scene.info().accel == ACCEL["grid"]:
             flags = (_lib.GRID_COMMIT_DEVICE if commit == "device" else 0) | (0 if install else _lib.GRID_NO_INSTALL)
             check(_lib.load().drt_scene_upload_device_grid(self.h, scene.h, flags), self.h,
                   "drt_scene_upload_device_grid")
-        elif commit == "host" and install:
+        elif build == "device" and commit == "host" and install:
             check(_lib.load().drt_scene_upload_device_bvh(self.h, scene.h), self.h, "drt_scene_upload_device_bvh")
         else:
-            flags = (_lib.BVH_COMMIT_DEVICE if commit == "device" else 0) | (0 if install else _lib.BVH_NO_INSTALL)
+            flags = ((_lib.BVH_COMMIT_DEVICE if commit == "device" else 0) | (0 if install else _lib.BVH_NO_INSTALL) |
+                     (_lib.BVH_BUILDER_PLOC_FLAG if build == "ploc" else 0))
             check(_lib.load().drt_scene_upload_device_bvh_ex(self.h, scene.h, flags), self.h,
                   "drt_scene_upload_device_bvh_ex")
         self.scene = scene
@@ -324,8 +330,8 @@ class Renderer:
                 for k, v in out.items()}
 
     def bvh_build_info(self):
-        """drt_bvh_build_info of the last build="device" upload: nodes, leaves, depth and the build /
-        fetch / commit times in ms."""
+        """drt_bvh_build_info of the last build="device" or "ploc" upload: nodes, leaves, depth, the build /
+        fetch / commit times in ms, the builder (0 LBVH, 1 PLOC) and PLOC's search and forced round counts."""
         i = _lib.DrtBvhBuildInfo()
         check(_lib.load().drt_get_bvh_build_info(self.h, C.byref(i)), self.h, "drt_get_bvh_build_info")
         return {n: (float(getattr(i, n)) if n.endswith("_ms") else int(getattr(i, n))) for n, _ in i._fields_}
@@ -523,10 +529,15 @@ class RendererGroup:
 
     def upload(self, scene: Scene, build="host"):
         """build="device": the tree is built once, on the first device (Renderer.upload), and the same
-        arrays are committed on every device."""
-        if build not in ("host", "device"):
-            raise ValueError(f"build must be 'host' or 'device', not {build!r}")
-        if build == "device" and scene.info().accel == ACCEL["grid"]:
+        arrays are committed on every device.  build="ploc": the same with the PLOC builder (BVH scenes)."""
+        if build not in ("host", "device", "ploc"):
+            raise ValueError(f"build must be 'host', 'device' or 'ploc', not {build!r}")
+        if build == "ploc" and scene.info().accel == ACCEL["grid"]:
+            raise ValueError("build='ploc' is a BVH builder: a Grid scene has one device builder, build='device'")
+        if build == "ploc":
+            self._check(_lib.load().drt_group_scene_upload_device_bvh_ex(self.h, scene.h, _lib.BVH_BUILDER_PLOC_FLAG),
+                        "drt_group_scene_upload_device_bvh_ex")
+        elif build == "device" and scene.info().accel == ACCEL["grid"]:
             self._check(_lib.load().drt_group_scene_upload_device_grid(self.h, scene.h),
                         "drt_group_scene_upload_device_grid")
         elif build == "device":

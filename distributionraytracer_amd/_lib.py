@@ -107,14 +107,15 @@ class DrtBvhNode(C.Structure):
 
 class DrtBvhBuildInfo(C.Structure):
     _fields_ = [("n_nodes", C.c_uint32), ("n_leaves", C.c_uint32), ("depth", C.c_uint32), ("build_ms", C.c_double),
-                ("fetch_ms", C.c_double), ("commit_ms", C.c_double)]
+                ("fetch_ms", C.c_double), ("commit_ms", C.c_double), ("builder", C.c_uint32), ("rounds", C.c_uint32),
+                ("forced_rounds", C.c_uint32)]
 
 
 class DrtBvhCommitInfo(C.Structure):
     _fields_ = [("on_device", C.c_uint32), ("has_wide", C.c_uint32), ("n_slots", C.c_uint32), ("n_wide", C.c_uint32)]
 
 
-BVH_COMMIT_DEVICE, BVH_NO_INSTALL = 1, 2  # drt_scene_upload_device_bvh_ex flags (include/drt_host.h)
+BVH_COMMIT_DEVICE, BVH_NO_INSTALL, BVH_BUILDER_PLOC_FLAG = 1, 2, 4  # drt_scene_upload_device_bvh_ex flags (drt_host.h)
 GRID_COMMIT_DEVICE, GRID_NO_INSTALL = 1, 2  # drt_scene_upload_device_grid flags (include/drt.h, drt_host.h)
 
 
@@ -135,6 +136,7 @@ SIGNATURES = {
     "drt_set_camera": (C.c_int, [_vp, C.POINTER(DrtCamera)]),
     "drt_upload_bvh": (C.c_int, [_vp, _vp, C.c_uint32, _u32, C.c_uint32]),
     "drt_build_bvh_device": (C.c_int, [_vp, _vp, _u32, C.POINTER(DrtBvhBuildInfo)]),
+    "drt_build_bvh_device_ex": (C.c_int, [_vp, C.c_int, C.c_int, _vp, _u32, C.POINTER(DrtBvhBuildInfo)]),
     "drt_get_bvh_build_info": (C.c_int, [_vp, C.POINTER(DrtBvhBuildInfo)]),
     "drt_build_bvh_device_commit": (C.c_int, [_vp, _vp, _u32, C.POINTER(DrtBvhBuildInfo)]),
     "drt_get_bvh_commit_info": (C.c_int, [_vp, C.POINTER(DrtBvhCommitInfo)]),
@@ -176,6 +178,7 @@ SIGNATURES = {
     "drt_scene_upload_device_bvh": (C.c_int, [_vp, _vp]),
     "drt_group_scene_upload_device_bvh": (C.c_int, [_vp, _vp]),
     "drt_scene_upload_device_bvh_ex": (C.c_int, [_vp, _vp, C.c_int]),
+    "drt_group_scene_upload_device_bvh_ex": (C.c_int, [_vp, _vp, C.c_int]),
     "drt_scene_set_grid": (C.c_int, [_vp, _i32, _f, _f, _i64, C.c_int64, _i32, C.c_int64]),
     "drt_scene_upload_device_grid": (C.c_int, [_vp, _vp, C.c_int]),
     "drt_group_scene_upload_device_grid": (C.c_int, [_vp, _vp]),

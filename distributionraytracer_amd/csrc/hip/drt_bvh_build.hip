@@ -9,6 +9,8 @@
 //   bvh_radix_tree    one lane per internal node of the binary radix tree over the sorted keys
 //   bvh_refit         one lane per sorted position climbs the parent links: boxes, depths, inner counts
 //   bvh_emit          renumbers into the drt_upload_bvh format (children adjacent, index > own index)
+// The slices of the scratch and the launch of the stages up to the sort (launch_bvh_sorted) are declared in
+// drt_bvh_arena.hpp: the PLOC builder (drt_bvh_ploc.hip) begins with the same stages.
 // The tree differs from the host's binned-SAH tree; it is a tree of the same shape rules (leaves of one or
 // two objects, children side by side), so the commit path of drt_upload_bvh takes it unchanged.
 //
@@ -22,52 +24,18 @@
 #include <cstdint>
 
 #include "../../../include/drt.h"
+#include "drt_bvh_arena.hpp"
 #include "drt_bvh_build.hpp"
 #include "drt_prim_device.hpp"
 #include "drt_scan_sort.hpp"
 
 namespace drt {
 
-namespace {
-
-// keys one sort workgroup ranks and stages in LDS: 16 KB of keys + 8 KB of payloads + 6 KB of counters, of
-// the 64 KB a workgroup may hold
-constexpr int kBvhSortTile = kTile;
-
-// node data of the refit, 8 words per node id: box min, box max, depth, inner count
-constexpr int kNodeWords = 8;
-
-struct SortPlan {
-  uint32_t skip[8];   // the pass's digit is the same for every key
-  uint32_t src[8];    // the pass reads buffer B (1) or A (0)
-  uint32_t final_sel; // the sorted keys / payloads are in buffer B (1) or A (0)
-  uint32_t pad[3];
-  uint32_t gbase[8][256];  // per pass: exclusive scan of the digit totals
-};
-
-// Everything the kernels share, sliced from one scratch allocation (bvh_build_scratch_bytes).
-struct Arena {
-  float4* pbox;        // 2 per primitive, scene order: (min, 0), (max, 0)
-  uint64_t* key[2];
-  uint32_t* pay[2];
-  uint32_t* table;     // 256 x n_wg digit counts, digit-major, scanned in place
-  uint32_t* ghist;     // 8 x 256
-  SortPlan* plan;
-  uint32_t* cbounds;   // ordered-integer centroid bounds: min xyz, max xyz
-  uint32_t* left;      // per internal node: child ids
-  uint32_t* right;
-  uint32_t* first;     // per internal node: covered range of sorted positions
-  uint32_t* last;
-  uint32_t* parent;    // per node id (internal i -> i, sorted position j -> n - 1 + j)
-  uint32_t* arrive;    // per internal node
-  uint32_t* ndata;     // kNodeWords per node id
-};
-
-Arena carve(void* scratch, uint32_t n, size_t* total) {
+BvhArena carve_bvh(void* scratch, uint32_t n, size_t* total) {
   const size_t nwg = div_up(n, kBvhSortTile);
   const size_t ids = 2 * (size_t)n;  // 2n - 1 used
   ScratchSlicer s{scratch};
-  Arena a;
+  BvhArena a;
   a.pbox = s.take<float4>(2 * (size_t)n);
   a.key[0] = s.take<uint64_t>(n);
   a.key[1] = s.take<uint64_t>(n);
@@ -88,12 +56,10 @@ Arena carve(void* scratch, uint32_t n, size_t* total) {
   return a;
 }
 
-// ---- small helpers ---------------------------------------------------------------------------------
-__device__ inline float smin(float a, float b) { return (b < a) ? b : a; }  // std::min, as drt_accel.cpp
-__device__ inline float smax(float a, float b) { return (a < b) ? b : a; }  // std::max
+namespace {
 
 // ---- stage 0: clear ---------------------------------------------------------------------------------
-__global__ __launch_bounds__(kThreads) void bvh_clear(Arena A, uint32_t n, uint32_t* info) {
+__global__ __launch_bounds__(kThreads) void bvh_clear(BvhArena A, uint32_t n, uint32_t* info) {
   const uint32_t i = blockIdx.x * kThreads + threadIdx.x;
   if (i < 2 * n - 1) A.parent[i] = kNone;
   if (i < n) A.arrive[i] = 0u;
@@ -107,7 +73,7 @@ __global__ __launch_bounds__(kThreads) void bvh_clear(Arena A, uint32_t n, uint3
 // AABB::centroid() (include/drt_scene.hpp): (min + max) / 2.0f per axis
 __device__ inline float centroid1(float lo, float hi) { return (lo + hi) / 2.0f; }
 
-__global__ __launch_bounds__(kThreads) void bvh_prim_bounds(const drt_prim* __restrict__ prims, uint32_t n, Arena A) {
+__global__ __launch_bounds__(kThreads) void bvh_prim_bounds(const drt_prim* __restrict__ prims, uint32_t n, BvhArena A) {
   const uint32_t i = blockIdx.x * kThreads + threadIdx.x;
   float lo[3] = {0.f, 0.f, 0.f}, hi[3] = {0.f, 0.f, 0.f};
   const bool valid = i < n;
@@ -155,7 +121,7 @@ __device__ inline uint32_t quant21(float c, uint32_t omin, uint32_t omax) {
   return x >= 2097151.0f ? 2097151u : (uint32_t)x;
 }
 
-__global__ __launch_bounds__(kThreads) void bvh_morton(uint32_t n, Arena A) {
+__global__ __launch_bounds__(kThreads) void bvh_morton(uint32_t n, BvhArena A) {
   __shared__ uint32_t h[8 * 256];
   for (int k = threadIdx.x; k < 8 * 256; k += kThreads) h[k] = 0u;
   __syncthreads();
@@ -178,7 +144,7 @@ __global__ __launch_bounds__(kThreads) void bvh_morton(uint32_t n, Arena A) {
 
 // ---- stage 3: stable LSD radix sort (why it is stable: radix_scatter_tile, drt_scan_sort.hpp) ------
 // One workgroup: which passes run, which buffer each reads, and each pass's digit bases.
-__global__ __launch_bounds__(kThreads) void bvh_sort_plan(uint32_t n, Arena A) {
+__global__ __launch_bounds__(kThreads) void bvh_sort_plan(uint32_t n, BvhArena A) {
   __shared__ uint32_t wave_tot[4];
   __shared__ uint32_t skip[8];
   const int t = threadIdx.x;
@@ -203,19 +169,19 @@ __global__ __launch_bounds__(kThreads) void bvh_sort_plan(uint32_t n, Arena A) {
 }
 
 // per-workgroup digit histogram of the tile -> table[digit * n_wg + wg]
-__global__ __launch_bounds__(kThreads) void bvh_sort_count(uint32_t n, uint32_t n_wg, int pass, Arena A) {
+__global__ __launch_bounds__(kThreads) void bvh_sort_count(uint32_t n, uint32_t n_wg, int pass, BvhArena A) {
   if (A.plan->skip[pass]) return;
   radix_count_tile<uint64_t>(A.key[A.plan->src[pass]], n, n_wg, pass, A.table);
 }
 
 // one workgroup per digit: exclusive scan of the digit's row of n_wg counts, offset by the digit's base
-__global__ __launch_bounds__(kThreads) void bvh_sort_scan(uint32_t n_wg, int pass, Arena A) {
+__global__ __launch_bounds__(kThreads) void bvh_sort_scan(uint32_t n_wg, int pass, BvhArena A) {
   if (A.plan->skip[pass]) return;
   (void)block_scan_array<uint32_t>(A.table + (size_t)blockIdx.x * n_wg, n_wg, A.plan->gbase[pass][blockIdx.x]);
 }
 
 // the tile's keys and payloads, ranked by digit, from the pass's source buffer to the other one
-__global__ __launch_bounds__(kThreads) void bvh_sort_scatter(uint32_t n, uint32_t n_wg, int pass, Arena A) {
+__global__ __launch_bounds__(kThreads) void bvh_sort_scatter(uint32_t n, uint32_t n_wg, int pass, BvhArena A) {
   if (A.plan->skip[pass]) return;
   const uint32_t sel = A.plan->src[pass];
   radix_scatter_tile<uint64_t>(A.key[sel], A.pay[sel], A.key[sel ^ 1u], A.pay[sel ^ 1u], n, n_wg, pass, A.table);
@@ -230,7 +196,7 @@ __device__ inline int delta(const uint64_t* __restrict__ k, uint64_t ki, int64_t
   return x ? __clzll((long long)x) : 64 + __clz((int)((uint32_t)i ^ (uint32_t)j));
 }
 
-__global__ __launch_bounds__(kThreads) void bvh_radix_tree(uint32_t n_u, Arena A) {
+__global__ __launch_bounds__(kThreads) void bvh_radix_tree(uint32_t n_u, BvhArena A) {
   const int64_t n = n_u, i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
   if (i >= n - 1) return;
   const uint64_t* __restrict__ k = A.key[A.plan->final_sel];
@@ -274,7 +240,7 @@ __device__ inline uint32_t node_load(const uint32_t* p) {
   return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-__global__ __launch_bounds__(kThreads) void bvh_refit(uint32_t n, Arena A) {
+__global__ __launch_bounds__(kThreads) void bvh_refit(uint32_t n, BvhArena A) {
   const uint32_t j = blockIdx.x * kThreads + threadIdx.x;  // a sorted position
   if (j >= n) return;
   const uint32_t* __restrict__ pay = A.pay[A.plan->final_sel];
@@ -330,7 +296,7 @@ __global__ __launch_bounds__(kThreads) void bvh_refit(uint32_t n, Arena A) {
 // An inner node of preorder rank r among the inner nodes keeps its children at 1 + 2r and 2 + 2r (the root
 // at 0).  rank(x) = rank(parent) + 1 + (x is the right child ? inner count of the left sibling : 0), summed
 // on a walk to the root: no lane needs another lane's result.
-__global__ __launch_bounds__(kThreads) void bvh_emit(uint32_t n, Arena A, drt_bvh_node* __restrict__ nodes,
+__global__ __launch_bounds__(kThreads) void bvh_emit(uint32_t n, BvhArena A, drt_bvh_node* __restrict__ nodes,
                                                      uint32_t* __restrict__ order, uint32_t* __restrict__ info) {
   const uint32_t id = blockIdx.x * kThreads + threadIdx.x;
   if (id < n) order[id] = A.pay[A.plan->final_sel][id];
@@ -388,14 +354,11 @@ __global__ __launch_bounds__(kThreads) void bvh_emit(uint32_t n, Arena A, drt_bv
 
 size_t bvh_build_scratch_bytes(uint32_t n_prims) {
   size_t total = 0;
-  (void)carve(nullptr, n_prims ? n_prims : 1u, &total);
+  (void)carve_bvh(nullptr, n_prims ? n_prims : 1u, &total);
   return total;
 }
 
-hipError_t launch_bvh_build(const drt_prim* d_prims, uint32_t n, void* d_scratch, drt_bvh_node* d_nodes,
-                            uint32_t* d_order, uint32_t* d_info, hipStream_t st) {
-  if (!d_prims || !d_scratch || !d_nodes || !d_order || !d_info || n == 0 || n > (1u << 26)) return hipErrorInvalidValue;
-  const Arena A = carve(d_scratch, n, nullptr);
+hipError_t launch_bvh_sorted(const drt_prim* d_prims, uint32_t n, const BvhArena& A, uint32_t* d_info, hipStream_t st) {
   const uint32_t per_prim = div_up(n, kThreads), per_id = div_up(2 * n - 1, kThreads);
   const uint32_t n_wg = div_up(n, kBvhSortTile);
   const uint32_t clear_grid = per_id > 8u ? per_id : 8u;  // also covers the 8 x 256 histogram
@@ -408,9 +371,17 @@ hipError_t launch_bvh_build(const drt_prim* d_prims, uint32_t n, void* d_scratch
     DRT_LAUNCH(bvh_sort_scan, 256, n_wg, pass, A);
     DRT_LAUNCH(bvh_sort_scatter, n_wg, n, n_wg, pass, A);
   }
+  return hipSuccess;
+}
+
+hipError_t launch_bvh_build(const drt_prim* d_prims, uint32_t n, void* d_scratch, drt_bvh_node* d_nodes,
+                            uint32_t* d_order, uint32_t* d_info, hipStream_t st) {
+  if (!d_prims || !d_scratch || !d_nodes || !d_order || !d_info || n == 0 || n > (1u << 26)) return hipErrorInvalidValue;
+  const BvhArena A = carve_bvh(d_scratch, n, nullptr);
+  if (const hipError_t e = launch_bvh_sorted(d_prims, n, A, d_info, st)) return e;
   if (n > 1) DRT_LAUNCH(bvh_radix_tree, div_up(n - 1, kThreads), n, A);
-  DRT_LAUNCH(bvh_refit, per_prim, n, A);
-  DRT_LAUNCH(bvh_emit, per_id, n, A, d_nodes, d_order, d_info);
+  DRT_LAUNCH(bvh_refit, div_up(n, kThreads), n, A);
+  DRT_LAUNCH(bvh_emit, div_up(2 * n - 1, kThreads), n, A, d_nodes, d_order, d_info);
   return hipSuccess;
 }
 

@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "drt_bvh_build.hpp"
+#include "drt_bvh_ploc.hpp"
 #include "drt_bvh_commit.hpp"
 #include "drt_grid_build.hpp"
 #include "drt_kernels.hpp"
@@ -1031,9 +1032,9 @@ static int raw_prims_to_device(drt_ctx* c, hipStream_t st) {
   return DRT_OK;
 }
 
-// drt_build_bvh_device and drt_build_bvh_device_commit: the build, then the host or the device commit
+// drt_build_bvh_device_ex: the build by either builder, then the host or the device commit
 static int build_bvh_device(drt_ctx* c, drt_bvh_node* nodes_out, uint32_t* order_out, drt_bvh_build_info* info,
-                            bool device_commit) {
+                            bool device_commit, bool ploc) {
   if (!c) return DRT_E_INVALID;
   if (!c->has_scene) DRT_FAIL(c, DRT_E_STATE, "upload the scene before building its BVH");
   if (c->n_prims <= 0) DRT_FAIL(c, DRT_E_INVALID, "a scene without primitives has no BVH");
@@ -1049,23 +1050,29 @@ static int build_bvh_device(drt_ctx* c, drt_bvh_node* nodes_out, uint32_t* order
   device_commit = device_commit && env_int("DRT_NODE_LAYOUT", 1) == 1 && env_int("DRT_WIDE_ORDER", 2) == 2 && kWideK == 4;
   const bool fetch = !device_commit || nodes_out || order_out;
   // the commit's scratch overlays the builder's, which is free once the build has ended
-  DRT_HIP(c, c->d_build.fit(std::max(bvh_build_scratch_bytes(n), device_commit ? bvh_commit_scratch_bytes(n) : 0)));
+  const size_t build_bytes = ploc ? ploc_build_scratch_bytes(n) : bvh_build_scratch_bytes(n);
+  DRT_HIP(c, c->d_build.fit(std::max(build_bytes, device_commit ? bvh_commit_scratch_bytes(n) : 0)));
   DRT_HIP(c, c->d_build_nodes.fit(sizeof(drt_bvh_node) * max_nodes));
   DRT_HIP(c, c->d_build_order.fit(sizeof(uint32_t) * n));
-  DRT_HIP(c, c->d_build_info.ensure(sizeof(uint32_t) * 4));
+  DRT_HIP(c, c->d_build_info.ensure(sizeof(uint32_t) * kPlocInfoWords));
   if (fetch) {
     DRT_HIP(c, c->h_build_nodes.ensure(sizeof(drt_bvh_node) * max_nodes));
     DRT_HIP(c, c->h_build_order.ensure(sizeof(uint32_t) * n));
   }
-  DRT_HIP(c, c->h_build_info.ensure(sizeof(uint32_t) * 4));
+  DRT_HIP(c, c->h_build_info.ensure(sizeof(uint32_t) * (kPlocInfoWords + 1)));  // + PLOC's live count
   hipStream_t st = c->stream;
+  uint32_t* hi = (uint32_t*)c->h_build_info.p;
   DRT_HIP(c, hipEventRecord(c->bev[0], st));
   if (const int rc = raw_prims_to_device(c, st)) return rc;
-  DRT_HIP(c, launch_bvh_build(c->d_prims_raw.as<drt_prim>(), n, c->d_build.p, c->d_build_nodes.as<drt_bvh_node>(),
-                              c->d_build_order.as<uint32_t>(), c->d_build_info.as<uint32_t>(), st));
+  if (ploc) {
+    DRT_HIP(c, launch_ploc_build(c->d_prims_raw.as<drt_prim>(), n, c->d_build.p, c->d_build_nodes.as<drt_bvh_node>(),
+                                 c->d_build_order.as<uint32_t>(), c->d_build_info.as<uint32_t>(), hi + kPlocInfoWords, st));
+  } else {
+    DRT_HIP(c, launch_bvh_build(c->d_prims_raw.as<drt_prim>(), n, c->d_build.p, c->d_build_nodes.as<drt_bvh_node>(),
+                                c->d_build_order.as<uint32_t>(), c->d_build_info.as<uint32_t>(), st));
+  }
   DRT_HIP(c, hipEventRecord(c->bev[1], st));
-  uint32_t* hi = (uint32_t*)c->h_build_info.p;
-  DRT_HIP(c, hipMemcpyAsync(hi, c->d_build_info.p, sizeof(uint32_t) * 4, hipMemcpyDeviceToHost, st));
+  DRT_HIP(c, hipMemcpyAsync(hi, c->d_build_info.p, sizeof(uint32_t) * (ploc ? kPlocInfoWords : 4), hipMemcpyDeviceToHost, st));
   DRT_HIP(c, hipStreamSynchronize(st));
   const uint32_t n_nodes = hi[0], n_leaves = hi[1], depth = hi[2];
   if (n_nodes == 0 || n_nodes > max_nodes || n_nodes != 2 * n_leaves - 1)
@@ -1098,6 +1105,9 @@ static int build_bvh_device(drt_ctx* c, drt_bvh_node* nodes_out, uint32_t* order
   bi.build_ms = build_ms;
   bi.fetch_ms = fetch_ms;
   bi.commit_ms = commit_ms;
+  bi.builder = ploc ? DRT_BVH_BUILDER_PLOC : DRT_BVH_BUILDER_LBVH;
+  bi.rounds = ploc ? hi[4] : 0u;
+  bi.forced_rounds = ploc ? hi[5] : 0u;
   c->build_info = bi;
   c->has_build_info = true;
   if (nodes_out) memcpy(nodes_out, hn, sizeof(drt_bvh_node) * n_nodes);
@@ -1107,11 +1117,20 @@ static int build_bvh_device(drt_ctx* c, drt_bvh_node* nodes_out, uint32_t* order
 }
 
 int drt_build_bvh_device(drt_ctx* c, drt_bvh_node* nodes_out, uint32_t* order_out, drt_bvh_build_info* info) {
-  return build_bvh_device(c, nodes_out, order_out, info, false);
+  return drt_build_bvh_device_ex(c, DRT_BVH_BUILDER_LBVH, 0, nodes_out, order_out, info);
 }
 
 int drt_build_bvh_device_commit(drt_ctx* c, drt_bvh_node* nodes_out, uint32_t* order_out, drt_bvh_build_info* info) {
-  return build_bvh_device(c, nodes_out, order_out, info, true);
+  return drt_build_bvh_device_ex(c, DRT_BVH_BUILDER_LBVH, DRT_BVH_EX_COMMIT_DEVICE, nodes_out, order_out, info);
+}
+
+int drt_build_bvh_device_ex(drt_ctx* c, int builder, int flags, drt_bvh_node* nodes_out, uint32_t* order_out,
+                            drt_bvh_build_info* info) {
+  if (!c) return DRT_E_INVALID;
+  if (builder != DRT_BVH_BUILDER_LBVH && builder != DRT_BVH_BUILDER_PLOC) DRT_FAIL(c, DRT_E_INVALID, "bad builder %d", builder);
+  if (flags & ~DRT_BVH_EX_COMMIT_DEVICE) DRT_FAIL(c, DRT_E_INVALID, "bad flags %d", flags);
+  return build_bvh_device(c, nodes_out, order_out, info, (flags & DRT_BVH_EX_COMMIT_DEVICE) != 0,
+                          builder == DRT_BVH_BUILDER_PLOC);
 }
 
 int drt_get_bvh_commit_info(const drt_ctx* c, drt_bvh_commit_info* info) {

@@ -218,6 +218,9 @@ typedef struct {
                         and that copy is inside this time                                             */
   double fetch_ms;   /* device -> host copy of nodes and order                  */
   double commit_ms;  /* host clock around the existing drt_upload_bvh commit    */
+  uint32_t builder;        /* DRT_BVH_BUILDER_LBVH or DRT_BVH_BUILDER_PLOC                              */
+  uint32_t rounds;         /* PLOC: search rounds run (0 for the LBVH)                                   */
+  uint32_t forced_rounds;  /* PLOC: rounds after them that paired neighbours whatever their boxes        */
 } drt_bvh_build_info;
 
 /* After drt_upload_scene: build a BVH of the resident primitives on the device and commit it
@@ -225,7 +228,21 @@ typedef struct {
  * NULL; otherwise they receive the tree.  DRT_E_STATE without a scene, DRT_E_INVALID for a scene without
  * primitives, DRT_E_OOM / DRT_E_HIP as elsewhere. */
 int drt_build_bvh_device(drt_ctx* ctx, drt_bvh_node* nodes_out, uint32_t* order_out, drt_bvh_build_info* info);
-/* The figures of the context's last drt_build_bvh_device (DRT_E_STATE before one). */
+/* The same with the builder chosen.  DRT_BVH_BUILDER_PLOC (csrc/hip/drt_bvh_ploc.hip) is parallel locally-ordered
+ * clustering (Meister and Bittner 2018) over the LBVH's Morton order: every round each cluster looks 8 clusters
+ * to each side for the one whose union box has the least surface, mutual nearest neighbours merge, and the
+ * cluster array is compacted; after 64 such rounds neighbours are paired whatever their boxes, so the depth is
+ * at most 91.  The tree has the LBVH's shape rules and goes through the same commits; it costs more rounds of
+ * kernels to build and has a lower surface-area cost (README.md, Use, for the measured figures).  flags: 0 or
+ * DRT_BVH_EX_COMMIT_DEVICE (the commit of drt_build_bvh_device_commit).  drt_build_bvh_device and
+ * drt_build_bvh_device_commit are this call with DRT_BVH_BUILDER_LBVH.  DRT_E_INVALID for another builder or
+ * flag. */
+#define DRT_BVH_BUILDER_LBVH 0
+#define DRT_BVH_BUILDER_PLOC 1
+#define DRT_BVH_EX_COMMIT_DEVICE 1
+int drt_build_bvh_device_ex(drt_ctx* ctx, int builder, int flags, drt_bvh_node* nodes_out, uint32_t* order_out,
+                            drt_bvh_build_info* info);
+/* The figures of the context's last device build (DRT_E_STATE before one). */
 int drt_get_bvh_build_info(const drt_ctx* ctx, drt_bvh_build_info* info);
 /* drt_build_bvh_device with the commit on the device too (csrc/hip/drt_bvh_commit.hip): the inner records and
  * their placement in 128-B lines, the leaf boxes, the primitive records in tree order and the 4-ary shadow

@@ -98,9 +98,12 @@ int drt_group_scene_upload_device_bvh(drt_group* g, drt_scene* s);
  * (drt_build_bvh_device_commit).  DRT_BVH_NO_INSTALL skips the fetch of the tree and drt_scene_set_bvh: the
  * host scene is not marked built by this call, so drt_scene_trace_cpu and drt_scene_bvh_export behave as on
  * an unbuilt scene (they build, or keep, the host's own tree, which is not the one the device walks).  Other
- * flag bits are DRT_E_INVALID.  The group form keeps the host commit. */
-enum { DRT_BVH_COMMIT_DEVICE = 1, DRT_BVH_NO_INSTALL = 2 };
+ * DRT_BVH_BUILDER_PLOC_FLAG builds with the PLOC builder (drt_build_bvh_device_ex, DRT_BVH_BUILDER_PLOC) instead
+ * of the LBVH, and composes with both.  Other flag bits are DRT_E_INVALID.  The group form keeps the host
+ * commit and takes DRT_BVH_BUILDER_PLOC_FLAG alone. */
+enum { DRT_BVH_COMMIT_DEVICE = 1, DRT_BVH_NO_INSTALL = 2, DRT_BVH_BUILDER_PLOC_FLAG = 4 };
 int drt_scene_upload_device_bvh_ex(drt_ctx* ctx, drt_scene* s, int flags);
+int drt_group_scene_upload_device_bvh_ex(drt_group* g, drt_scene* s, int flags);
 /* Install a caller's cell lists as a Grid scene's grid (the inverse of drt_scene_grid_export*): dims, box, CSR
  * starts (n_starts = nx*ny*nz + 1) and cell objects (scene indices).  No geometry is computed.  DRT_E_INVALID,
  * the scene unchanged, unless dims > 0, the starts run monotonically from 0 to n_refs, n_starts fits dims and

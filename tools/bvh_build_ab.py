@@ -2,7 +2,9 @@
 the host's binned-SAH build (drt_scene_build, tree-identical to the reference) against the device LBVH
 (drt_build_bvh_device) committed by the host, and the same LBVH committed on the device
 (drt_build_bvh_device_commit) with and without installing the tree in the host scene; the headline frame on
-each committed tree.
+each committed tree.  The PLOC builder (drt_build_bvh_device_ex, build="ploc") is two more arms, ploc (host commit)
+and ploc_dcommit (device commit), with its round count, and the builds line carries each tree's surface-area
+cost: (sum of inner box surfaces + sum of leaf box surfaces x objects) / the root's surface.
 
 Two JSON lines:
   builds  --rounds interleaved rounds after one warm-up round, each on a fresh Scene: the host build's ms
@@ -14,7 +16,7 @@ Two JSON lines:
           (HIP events), Mrays/s = (closest + shadow traversals of a stats frame) / median ms, the
           shadow-query stream's ms (drt_frame_stage_times) and the binary tree's depth.
 
-  python tools/bvh_build_ab.py [--rounds 10] [--tris 1000000] > profiles/gpu_bvh_commit.jsonl
+  python tools/bvh_build_ab.py [--rounds 10] [--tris 1000000] > profiles/gpu_bvh_ploc.jsonl
 """
 import argparse
 import json
@@ -47,12 +49,20 @@ def tree_depth(tree):
     return depth
 
 
+def sa_cost(tree):
+    e = tree["boxes"][:, 3:].astype(np.float64) - tree["boxes"][:, :3]
+    area = e[:, 0] * e[:, 1] + e[:, 1] * e[:, 2] + e[:, 2] * e[:, 0]
+    leaf = tree["leaf"].astype(bool)
+    return round(float((area[~leaf].sum() + (area[leaf] * tree["nobjs"][leaf]).sum()) / area[0]), 3)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=10)
     ap.add_argument("--tris", type=int, default=1_000_000)
     ap.add_argument("--res", type=int, default=512)
     ap.add_argument("--spp", type=int, default=64)
+    ap.add_argument("--ploc-radius", type=int, default=8, help="kPlocRadius of the library under test (a label)")
     args = ap.parse_args()
     tris = bench.synthetic_triangles(args.tris)
 
@@ -61,7 +71,8 @@ def main():
         bench.populate(s, tris, args.res, args.spp)
         return s
 
-    dev_arms = {"device": {}, "dcommit": {"commit": "device"}, "dcommit_noinstall": {"commit": "device", "install": False}}
+    dev_arms = {"device": {}, "dcommit": {"commit": "device"}, "dcommit_noinstall": {"commit": "device", "install": False},
+                "ploc": {"build": "ploc"}, "ploc_dcommit": {"build": "ploc", "commit": "device"}}
     ctx = {a: drt.Renderer(0) for a in ("host", *dev_arms)}
     rows = {"host_build_ms": [], "host_upload_wall_ms": []}
     rows.update({f"{a}_{k}_ms": [] for a in dev_arms for k in ("build", "fetch", "commit", "upload_wall")})
@@ -80,7 +91,7 @@ def main():
         for a, kw in dev_arms.items():
             d = fresh()
             t3 = time.perf_counter()
-            ctx[a].upload(d, build="device", **kw)
+            ctx[a].upload(d, **{"build": "device", **kw})
             t4 = time.perf_counter()
             scenes[a] = d
             if rnd == 0:
@@ -94,6 +105,9 @@ def main():
     out["host_build_over_device_build_plus_fetch"] = round(
         out["host_build_ms"]["median"] / (out["device_build_ms"]["median"] + out["device_fetch_ms"]["median"]), 1)
     out["commit_info"] = {a: ctx[a].bvh_commit_info() for a in dev_arms}
+    out["ploc_rounds"] = {k: ctx["ploc"].bvh_build_info()[k] for k in ("rounds", "forced_rounds")}
+    out["ploc_radius"] = args.ploc_radius
+    out["sa_cost"] = {a: sa_cost(scenes[a].bvh_export()) for a in ("host", "device", "ploc")}
     print(json.dumps(out), flush=True)
 
     arms = tuple(ctx)
@@ -125,6 +139,8 @@ def main():
         out[f"{a}_over_host_frame_rate"] = round(out["host"]["frame_ms"]["median"] / out[a]["frame_ms"]["median"], 3)
     out["dcommit_over_device_frame_rate"] = round(
         out["device"]["frame_ms"]["median"] / out["dcommit"]["frame_ms"]["median"], 3)
+    out["ploc_over_device_frame_rate"] = round(out["device"]["frame_ms"]["median"] / out["ploc"]["frame_ms"]["median"], 3)
+    out["ploc_radius"] = args.ploc_radius
     print(json.dumps(out), flush=True)
     for r in ctx.values():
         r.close()
