@@ -274,7 +274,7 @@ class Renderer:
         except Exception:
             pass
 
-    def upload(self, scene: Scene, build="host", commit="host", install=True):
+    def upload(self, scene: Scene, build="host", commit="host", install=True, shadow_tree=None):
         """build="host": the reference's binned-SAH tree, built on the CPU (drt_scene_build) if the scene
         is not built yet.  build="device" (BVH scenes): a linear BVH built by HIP kernels from the
         primitives on the device (drt_build_bvh_device) and installed in `scene` too — far quicker to
@@ -284,8 +284,13 @@ class Renderer:
         comes back from the device, and scene.trace_cpu / scene.bvh_export behave as on an unbuilt scene.
         A Grid scene with build="device" gets its grid from HIP kernels too (drt_build_grid_device): exactly
         the host's cell lists, bit for bit, committed by drt_upload_grid (commit="host") or by kernels
-        (commit="device").  No shadow tree is built for it: shadow queries take the Grid walk, which renders
-        the same frame at a lower rate.
+        (commit="device").  shadow_tree="device" or "ploc" (Grid scenes with build="device" only) also builds
+        its shadow tree on the device: the LBVH or the PLOC builder's tree of the primitives, committed by
+        HIP kernels (csrc/hip/drt_grid_tree_commit.hip) with the cell ranges the grid build left there, and
+        with install=True stored in `scene`, so that a later upload(scene) commits the same tree on the host.
+        grid_build_info()["shadow_tree"] says which tree is resident (0: none — a scene with other
+        primitives than triangles, DRT_GRID_SHADOW_TREE=0, a tree the commit refused).  With shadow_tree=None
+        no tree is built: shadow queries take the Grid walk, which renders the same frame at a lower rate.
         build="ploc" (BVH scenes only): as build="device" with the PLOC builder (drt_build_bvh_device_ex,
         csrc/hip/drt_bvh_ploc.hip) in place of the LBVH: more kernel rounds to build, a tree of lower
         surface-area cost (README.md, Use); commit and install as with build="device"."""
@@ -295,12 +300,17 @@ class Renderer:
             raise ValueError(f"commit must be 'host' or 'device', not {commit!r}")
         if build == "host" and (commit == "device" or not install):
             raise ValueError("commit='device' and install=False need build='device' or 'ploc'")
+        if shadow_tree not in (None, "device", "ploc"):
+            raise ValueError(f"shadow_tree must be None, 'device' or 'ploc', not {shadow_tree!r}")
         if build == "ploc" and scene.info().accel == ACCEL["grid"]:
             raise ValueError("build='ploc' is a BVH builder: a Grid scene has one device builder, build='device'")
+        if shadow_tree is not None and (build == "host" or scene.info().accel != ACCEL["grid"]):
+            raise ValueError("shadow_tree needs a Grid scene and build='device'")
         if build == "host":
             check(_lib.load().drt_scene_upload(self.h, scene.h), self.h, "drt_scene_upload")
         elif scene.info().accel == ACCEL["grid"]:
-            flags = (_lib.GRID_COMMIT_DEVICE if commit == "device" else 0) | (0 if install else _lib.GRID_NO_INSTALL)
+            flags = ((_lib.GRID_COMMIT_DEVICE if commit == "device" else 0) | (0 if install else _lib.GRID_NO_INSTALL) |
+                     {None: 0, "device": _lib.GRID_SHADOW_LBVH, "ploc": _lib.GRID_SHADOW_PLOC}[shadow_tree])
             check(_lib.load().drt_scene_upload_device_grid(self.h, scene.h, flags), self.h,
                   "drt_scene_upload_device_grid")
         elif build == "device" and commit == "host" and install:
@@ -322,10 +332,11 @@ class Renderer:
 
     def grid_build_info(self):
         """drt_grid_build_info of the last build="device" upload of a Grid scene: dims, box, cells,
-        references, the build / fetch / commit times in ms and whether the device committed."""
+        references, the build / fetch / commit times in ms, whether the device committed, and the shadow tree
+        built with it (0 none, 1 LBVH, 2 PLOC; its figures: bvh_build_info())."""
         i = _lib.DrtGridBuildInfo()
         check(_lib.load().drt_get_grid_build_info(self.h, C.byref(i)), self.h, "drt_get_grid_build_info")
-        out = {n: getattr(i, n) for n, _ in i._fields_ if n != "reserved"}
+        out = {n: getattr(i, n) for n, _ in i._fields_}
         return {k: (tuple(v) if k in ("dims", "bmin", "bmax") else (float(v) if k.endswith("_ms") else int(v)))
                 for k, v in out.items()}
 
@@ -529,7 +540,9 @@ class RendererGroup:
 
     def upload(self, scene: Scene, build="host"):
         """build="device": the tree is built once, on the first device (Renderer.upload), and the same
-        arrays are committed on every device.  build="ploc": the same with the PLOC builder (BVH scenes)."""
+        arrays are committed on every device.  build="ploc": the same with the PLOC builder (BVH scenes).
+        Renderer.upload's shadow_tree (a Grid scene's shadow tree built on the device) is not offered here:
+        a group's device-built grid answers shadow queries by the Grid walk."""
         if build not in ("host", "device", "ploc"):
             raise ValueError(f"build must be 'host', 'device' or 'ploc', not {build!r}")
         if build == "ploc" and scene.info().accel == ACCEL["grid"]:

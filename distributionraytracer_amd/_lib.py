@@ -117,12 +117,13 @@ class DrtBvhCommitInfo(C.Structure):
 
 BVH_COMMIT_DEVICE, BVH_NO_INSTALL, BVH_BUILDER_PLOC_FLAG = 1, 2, 4  # drt_scene_upload_device_bvh_ex flags (drt_host.h)
 GRID_COMMIT_DEVICE, GRID_NO_INSTALL = 1, 2  # drt_scene_upload_device_grid flags (include/drt.h, drt_host.h)
+GRID_SHADOW_LBVH, GRID_SHADOW_PLOC = 4, 8   # ... and the shadow tree built with the grid (include/drt.h)
 
 
 class DrtGridBuildInfo(C.Structure):
     _fields_ = [("dims", C.c_int32 * 3), ("bmin", C.c_float * 3), ("bmax", C.c_float * 3), ("n_cells", C.c_int64),
                 ("n_refs", C.c_int64), ("build_ms", C.c_double), ("fetch_ms", C.c_double), ("commit_ms", C.c_double),
-                ("on_device", C.c_uint32), ("reserved", C.c_uint32)]
+                ("on_device", C.c_uint32), ("shadow_tree", C.c_uint32)]
 
 
 # Every symbol include/drt.h and include/drt_host.h declare, with its ctypes signature.

@@ -20,11 +20,8 @@
 //                       stores; two neighbouring lanes cover one line
 //   commit_leaf_prims   one lane per node / primitive: leaf boxes; 48-B records packed from the raw
 //                       primitives as pack_prim does, gathered into tree order
-//   commit_wide_level   once per level of the 4-ary tree: a lane per wide root of the frontier collapses its
-//                       node and appends the inner children to the next frontier, one atomic per wave
-//   commit_wide_count / commit_scan / commit_wide_place
-//                       a wide root's record index = the exclusive prefix sum of the marks in node-slot order
-//                       (only the set of marks depends on arrival order, the placement does not)
+//   launch_wide_marks   the 4-ary tree's roots and their record indices (drt_bvh_wide.hpp, shared with the
+//                       Grid scene's shadow tree, drt_grid_tree_commit.hip)
 //   commit_wide_write   one lane per wide record: collapse again, order, quantise in double, 64-B record
 //
 // Stages are kernel boundaries on one stream; no lane waits for another.  The frontier kernels size their
@@ -35,6 +32,7 @@
 #include <cstdint>
 
 #include "drt_bvh_commit.hpp"
+#include "drt_bvh_wide.hpp"
 #include "drt_prim_device.hpp"
 #include "drt_scan_sort.hpp"
 
@@ -42,20 +40,12 @@ namespace drt {
 
 namespace {
 
-constexpr int kMaxLevels = 128;         // level counters (the host launches far fewer levels)
-constexpr uint32_t kLevelGridMax = 1024;  // workgroups of a frontier launch (grid-stride beyond)
-
 struct Arena {
   uint32_t* rank_slot;  // per inner rank: its node slot
   uint32_t* head;       // per node slot: 1 = an inner node whose record starts a line
   uint32_t* pos;        // per node slot (inner): its record slot
   uint32_t* slot_node;  // per record slot: its node slot, kNone for padding
-  uint32_t* wmark;      // per node slot: 1 = root of a 4-ary node
-  uint32_t* widx;       // per node slot (wide root): its 4-ary record index
-  uint32_t* wlist;      // per 4-ary record: its node slot
-  uint32_t* frontier[2];
-  uint32_t* wg_counts;  // per workgroup of a node-slot launch
-  uint32_t* level_cnt;  // kMaxLevels frontier sizes
+  WideArena w;          // the 4-ary tree's marks, indices, frontiers and counts (drt_bvh_wide.hpp)
 };
 
 Arena carve(void* scratch, uint32_t n, size_t* total) {
@@ -66,26 +56,12 @@ Arena carve(void* scratch, uint32_t n, size_t* total) {
   a.head = s.take<uint32_t>(nodes);
   a.pos = s.take<uint32_t>(nodes);
   a.slot_node = s.take<uint32_t>(2 * inner);
-  a.wmark = s.take<uint32_t>(nodes);
-  a.widx = s.take<uint32_t>(nodes);
-  a.wlist = s.take<uint32_t>(inner);
-  a.frontier[0] = s.take<uint32_t>(inner);
-  a.frontier[1] = s.take<uint32_t>(inner);
-  a.wg_counts = s.take<uint32_t>((nodes + kThreads - 1) / kThreads + 1);
-  a.level_cnt = s.take<uint32_t>(kMaxLevels);
+  a.w = carve_wide(s, n);
   if (total) *total = s.used;
   return a;
 }
 
 // ---- helpers ---------------------------------------------------------------------------------------
-// box surface as drt_upload_bvh's area(): double, x*y + y*z + z*x, unfused
-__device__ inline double surface(const drt_bvh_node* __restrict__ nodes, uint32_t i) {
-  const drt_bvh_node& nd = nodes[i];
-  const double x = (double)nd.bmax[0] - nd.bmin[0], y = (double)nd.bmax[1] - nd.bmin[1],
-               z = (double)nd.bmax[2] - nd.bmin[2];
-  return x * y + y * z + z * x;
-}
-
 // the inner child of larger surface of the node whose children are l and l + 1 (the left one on a tie),
 // kNone if both are leaves
 __device__ inline uint32_t larger_child(const drt_bvh_node* __restrict__ nodes, uint32_t l) {
@@ -94,9 +70,6 @@ __device__ inline uint32_t larger_child(const drt_bvh_node* __restrict__ nodes, 
   return li ? l : (ri ? l + 1 : kNone);
 }
 
-__device__ inline uint32_t node_desc(const drt_bvh_node& nd, const uint32_t* __restrict__ inner_index, uint32_t i) {
-  return nd.leaf ? leaf_desc(nd.index, nd.n_objs) : inner_index[i];
-}
 
 // ---- stage 1: binary records and their placement ---------------------------------------------------
 __global__ __launch_bounds__(kThreads) void commit_index(const drt_bvh_node* __restrict__ nodes, uint32_t n_nodes,
@@ -104,7 +77,7 @@ __global__ __launch_bounds__(kThreads) void commit_index(const drt_bvh_node* __r
   const uint32_t s = blockIdx.x * kThreads + threadIdx.x;
   const uint32_t n_inner = (n_nodes - 1) / 2;
   const bool root_inner = !nodes[0].leaf;
-  if (s < (uint32_t)kMaxLevels) A.level_cnt[s] = (s == 0 && root_inner) ? 1u : 0u;
+  if (s < (uint32_t)kMaxLevels) A.w.level_cnt[s] = (s == 0 && root_inner) ? 1u : 0u;
   if (s == 0) {
     const drt_bvh_node r = nodes[0];
     BvhCommitStatus st{};
@@ -115,10 +88,10 @@ __global__ __launch_bounds__(kThreads) void commit_index(const drt_bvh_node* __r
       st.root_box[3 + a] = r.bmax[a];
     }
     *status = st;
-    if (root_inner) A.frontier[0][0] = 0u;
+    if (root_inner) A.w.frontier[0][0] = 0u;
   }
   if (s >= n_nodes) return;
-  A.wmark[s] = (s == 0 && root_inner) ? 1u : 0u;
+  A.w.wmark[s] = (s == 0 && root_inner) ? 1u : 0u;
   const drt_bvh_node& nd = nodes[s];
   if (!nd.leaf) {
     const uint32_t rank = (nd.index - 1u) >> 1;
@@ -147,13 +120,7 @@ __global__ __launch_bounds__(kThreads) void commit_heads(const drt_bvh_node* __r
   if (s < n_nodes) A.head[s] = head ? 1u : 0u;
   uint32_t total;
   (void)block_flag_scan(head, wave_tot, total);
-  if (threadIdx.x == 0) A.wg_counts[blockIdx.x] = total;
-}
-
-// One workgroup: counts[0 .. n) -> their exclusive scan in place, the total to *total_out.
-__global__ __launch_bounds__(kThreads) void commit_scan(uint32_t* counts, uint32_t n, uint32_t* total_out) {
-  const uint32_t total = block_scan_array<uint32_t>(counts, n, 0u);
-  if (threadIdx.x == 0) *total_out = total;
+  if (threadIdx.x == 0) A.w.wg_counts[blockIdx.x] = total;
 }
 
 __global__ __launch_bounds__(kThreads) void commit_place(const drt_bvh_node* __restrict__ nodes, uint32_t n_nodes,
@@ -163,7 +130,7 @@ __global__ __launch_bounds__(kThreads) void commit_place(const drt_bvh_node* __r
   const uint32_t n_inner = (n_nodes - 1) / 2;
   const bool head = s < n_nodes && A.head[s] != 0u;
   uint32_t total;
-  const uint32_t line = A.wg_counts[blockIdx.x] + block_flag_scan(head, wave_tot, total);
+  const uint32_t line = A.w.wg_counts[blockIdx.x] + block_flag_scan(head, wave_tot, total);
   if (!head || line >= n_inner) return;
   const uint32_t l = nodes[s].index;
   if (l + 1u >= n_nodes) return;
@@ -236,205 +203,7 @@ __global__ __launch_bounds__(kThreads) void commit_leaf_prims(const drt_bvh_node
   prims[3 * (size_t)i + 2] = q2;
 }
 
-// ---- stage 3: the 4-ary shadow tree ----------------------------------------------------------------
-// build_wide's collapse at its defaults: the two children of node s, the inner one of largest surface
-// replaced by its two until there are four or only leaves; then ascending surface, stable.
-struct Collapse {
-  uint32_t ch[4];
-  double area[4];
-  bool leaf[4];
-  int n;
-};
-
-__device__ inline void collapse_set(Collapse& C, int k, const drt_bvh_node* __restrict__ nodes, uint32_t c) {
-#pragma unroll
-  for (int j = 0; j < 4; j++)
-    if (j == k) {
-      C.ch[j] = c;
-      C.leaf[j] = nodes[c].leaf != 0u;
-      C.area[j] = surface(nodes, c);
-    }
-}
-
-__device__ inline void collapse(Collapse& C, const drt_bvh_node* __restrict__ nodes, uint32_t s, uint32_t n_nodes) {
-#pragma unroll
-  for (int j = 0; j < 4; j++) {
-    C.ch[j] = 0u;
-    C.area[j] = 0.0;
-    C.leaf[j] = true;
-  }
-  const uint32_t l = nodes[s].index;
-  C.n = 0;
-  if (l + 1u >= n_nodes) return;
-  collapse_set(C, 0, nodes, l);
-  collapse_set(C, 1, nodes, l + 1u);
-  C.n = 2;
-#pragma unroll
-  for (int round = 0; round < 2; round++) {
-    int best = -1;
-    double ba = -1.0;
-#pragma unroll
-    for (int k = 0; k < 4; k++)
-      if (k < C.n && !C.leaf[k] && C.area[k] > ba) {
-        ba = C.area[k];
-        best = k;
-      }
-    if (best < 0) break;
-    uint32_t c = 0u;
-#pragma unroll
-    for (int k = 0; k < 4; k++)
-      if (k == best) c = C.ch[k];
-    const uint32_t cl = nodes[c].index;
-    if (cl + 1u >= n_nodes) break;
-    collapse_set(C, best, nodes, cl);
-    collapse_set(C, C.n, nodes, cl + 1u);
-    C.n++;
-  }
-}
-
-// stable insertion sort by ascending surface (std::stable_sort's result for this comparison)
-__device__ inline void collapse_sort(Collapse& C) {
-#pragma unroll
-  for (int i = 1; i < 4; i++) {
-#pragma unroll
-    for (int j = i; j > 0; j--) {
-      if (i < C.n && C.area[j] < C.area[j - 1]) {
-        const uint32_t c = C.ch[j]; C.ch[j] = C.ch[j - 1]; C.ch[j - 1] = c;
-        const double a = C.area[j]; C.area[j] = C.area[j - 1]; C.area[j - 1] = a;
-        const bool f = C.leaf[j]; C.leaf[j] = C.leaf[j - 1]; C.leaf[j - 1] = f;
-      }
-    }
-  }
-}
-
-__global__ __launch_bounds__(kThreads) void commit_wide_level(const drt_bvh_node* __restrict__ nodes, uint32_t n_nodes,
-                                                              Arena A, int level, BvhCommitStatus* status) {
-  const uint32_t cnt = A.level_cnt[level];
-  const uint32_t n_inner = (n_nodes - 1) / 2;
-  const uint32_t* __restrict__ in = A.frontier[level & 1];
-  uint32_t* __restrict__ out = A.frontier[(level + 1) & 1];
-  const int lane = threadIdx.x & 63;
-  if (cnt && blockIdx.x == 0 && threadIdx.x == 0) status->wide_depth = (uint32_t)level + 1u;
-  // the trip count is the same for every lane of a workgroup
-  for (uint32_t base = blockIdx.x * kThreads; base < cnt && base < n_inner; base += gridDim.x * kThreads) {
-    const uint32_t i = base + threadIdx.x;
-    Collapse C;
-    C.n = 0;
-#pragma unroll
-    for (int j = 0; j < 4; j++) {
-      C.ch[j] = 0u;
-      C.leaf[j] = true;
-    }
-    if (i < cnt && i < n_inner) {
-      const uint32_t s = in[i];
-      if (s < n_nodes) collapse(C, nodes, s, n_nodes);
-    }
-    uint32_t mine = 0u;
-#pragma unroll
-    for (int k = 0; k < 4; k++) mine += (k < C.n && !C.leaf[k]) ? 1u : 0u;
-    // one atomic per wave: the wave's inner children take a contiguous run of the next frontier
-    const uint32_t inc = wave_scan_incl(mine);
-    const uint32_t wave_total = __shfl(inc, 63, 64);
-    uint32_t run = 0u;
-    if (lane == 63 && wave_total) run = atomicAdd(&A.level_cnt[level + 1], wave_total);
-    run = __shfl(run, 63, 64);
-    uint32_t at = run + inc - mine;
-#pragma unroll
-    for (int k = 0; k < 4; k++)
-      if (k < C.n && !C.leaf[k]) {
-        if (at < n_inner) out[at] = C.ch[k];
-        at++;
-        A.wmark[C.ch[k]] = 1u;
-      }
-  }
-}
-
-__global__ __launch_bounds__(kThreads) void commit_wide_count(uint32_t n_nodes, Arena A) {
-  __shared__ uint32_t wave_tot[4];
-  const uint32_t s = blockIdx.x * kThreads + threadIdx.x;
-  uint32_t total;
-  (void)block_flag_scan(s < n_nodes && A.wmark[s] != 0u, wave_tot, total);
-  if (threadIdx.x == 0) A.wg_counts[blockIdx.x] = total;
-}
-
-__global__ __launch_bounds__(kThreads) void commit_wide_place(uint32_t n_nodes, Arena A) {
-  __shared__ uint32_t wave_tot[4];
-  const uint32_t s = blockIdx.x * kThreads + threadIdx.x;
-  const uint32_t n_inner = (n_nodes - 1) / 2;
-  const bool mark = s < n_nodes && A.wmark[s] != 0u;
-  uint32_t total;
-  const uint32_t w = A.wg_counts[blockIdx.x] + block_flag_scan(mark, wave_tot, total);
-  if (!mark || w >= n_inner) return;
-  A.widx[s] = w;
-  A.wlist[w] = s;
-}
-
-// quantize_axis of drt_capi.hip for four children, in the same double arithmetic.  A function of its own (not
-// inlined three times into the record kernel), its results by value.
-struct AxisPlanes {
-  float p;
-  uint32_t ebits, qlo, qhi;
-  bool ok;
-};
-
-__device__ __noinline__ AxisPlanes quantize_axis(double l0, double l1, double l2, double l3, double h0, double h1,
-                                                 double h2, double h3, int n) {
-  const double lo[4] = {l0, l1, l2, l3}, hi[4] = {h0, h1, h2, h3};
-  AxisPlanes R;
-  R.p = 0.f;
-  R.ebits = R.qlo = R.qhi = 0u;
-  R.ok = false;
-  double nlo = lo[0], nhi = hi[0];
-#pragma unroll
-  for (int k = 1; k < 4; k++)
-    if (k < n) {
-      nlo = lo[k] < nlo ? lo[k] : nlo;  // std::min / std::max
-      nhi = nhi < hi[k] ? hi[k] : nhi;
-    }
-  if (!isfinite(nlo) || !isfinite(nhi) || nhi < nlo) return R;
-  if (fabs(nlo) > 0x1p59 || fabs(nhi) > 0x1p59) return R;
-  int e0 = -126;
-  if (nhi > nlo) {
-    const int e = ilogb((nhi - nlo) / 255.0) - 1;
-    e0 = e > -126 ? e : -126;
-  }
-  for (int E = e0; E <= 120; E++) {
-    const double s = ldexp(1.0, E);
-    const double k0 = floor(nlo / s);
-    if (fabs(k0) + 256.0 >= 16777216.0) continue;
-    const float pf = (float)(k0 * s), sf = (float)s;
-    if ((double)pf != k0 * s) continue;
-    if (E > 50) return R;
-    uint32_t L = 0u, H = 0u;
-    bool ok = true;
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-      if (k >= n) {  // unused slot: an inverted box
-        L |= 255u << (8 * k);
-      } else {
-        const double ql = floor(lo[k] / s) - k0, qh = ceil(hi[k] / s) - k0;
-        const bool in = ql >= 0.0 && qh <= 255.0;
-        // the device decodes with one FMA; every value here is exact, so check it as the device does
-        const float dl = fmaf((float)ql, sf, pf), dh = fmaf((float)qh, sf, pf);
-        const bool covers = (double)dl <= lo[k] && (double)dh >= hi[k] && isfinite(dl) && isfinite(dh);
-        ok = ok && in && covers;
-        if (in) {
-          L |= (uint32_t)ql << (8 * k);
-          H |= (uint32_t)qh << (8 * k);
-        }
-      }
-    }
-    if (!ok) continue;
-    R.p = pf;
-    R.ebits = (uint32_t)(E + 127);
-    R.qlo = L;
-    R.qhi = H;
-    R.ok = true;
-    return R;
-  }
-  return R;
-}
-
+// ---- stage 3: the 4-ary shadow tree (drt_bvh_wide.hpp) ---------------------------------------------
 __global__ __launch_bounds__(kThreads) void commit_wide_write(const drt_bvh_node* __restrict__ nodes, uint32_t n_nodes,
                                                               Arena A, BvhCommitStatus* status,
                                                               uint4* __restrict__ wide) {
@@ -443,45 +212,9 @@ __global__ __launch_bounds__(kThreads) void commit_wide_write(const drt_bvh_node
   uint32_t n_wide = status->n_wide;
   if (n_wide > n_inner) n_wide = n_inner;
   if (w >= n_wide) return;
-  const uint32_t s = A.wlist[w];
-  uint4 s0 = make_uint4(0u, 0u, 0u, 0u), s1 = s0, s2 = s0, s3 = s0;
-  bool ok = s < n_nodes;
-  if (ok) {
-    Collapse C;
-    collapse(C, nodes, s, n_nodes);
-    collapse_sort(C);
-    float p[3] = {0.f, 0.f, 0.f};
-    uint32_t q[6] = {0u, 0u, 0u, 0u, 0u, 0u}, ebits = 0u;
-#pragma unroll
-    for (int a = 0; a < 3; a++) {
-      double lo[4] = {0.0, 0.0, 0.0, 0.0}, hi[4] = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-      for (int k = 0; k < 4; k++)
-        if (k < C.n) {
-          lo[k] = (double)nodes[C.ch[k]].bmin[a];
-          hi[k] = (double)nodes[C.ch[k]].bmax[a];
-        }
-      const AxisPlanes R = quantize_axis(lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3], C.n);
-      ok = ok && R.ok;
-      p[a] = R.p;
-      q[2 * a] = R.qlo;
-      q[2 * a + 1] = R.qhi;
-      ebits |= R.ebits << (8 * a);
-    }
-    uint32_t desc[4] = {0u, 0u, 0u, 0u};
-#pragma unroll
-    for (int k = 0; k < 4; k++)
-      if (k < C.n) desc[k] = node_desc(nodes[C.ch[k]], A.widx, C.ch[k]);
-    if (ok && C.n >= 2) {
-      s0 = make_uint4(__float_as_uint(p[0]), __float_as_uint(p[1]), __float_as_uint(p[2]), ebits);
-      s1 = make_uint4(q[0], q[1], q[2], q[3]);
-      s2 = make_uint4(q[4], q[5], 0u, 0u);
-      s3 = make_uint4(desc[0], desc[1], desc[2], desc[3]);
-    } else {
-      ok = false;
-    }
-  }
-  if (!ok) atomicOr(&status->flags, (uint32_t)kCommitNoQuant);  // the host keeps the binary tree for shadow queries
+  uint4 s0, s1, s2, s3;
+  if (!wide_record(nodes, n_nodes, A.w.wlist[w], A.w.widx, 0.0, s0, s1, s2, s3))
+    atomicOr(&status->flags, (uint32_t)kCommitNoQuant);  // the host keeps the binary tree for shadow queries
   uint4* out = wide + 4 * (size_t)w;
   out[0] = s0;
   out[1] = s1;
@@ -511,7 +244,7 @@ hipError_t launch_bvh_commit(const BvhCommitArgs& a, hipStream_t st) {
   DRT_LAUNCH(commit_index, per_node, a.nodes, n_nodes, A, a.status);
   if (n_inner > 0) {
     DRT_LAUNCH(commit_heads, per_node, a.nodes, n_nodes, A);
-    DRT_LAUNCH(commit_scan, 1, A.wg_counts, per_node, &a.status->n_lines);
+    DRT_LAUNCH(commit_scan, 1, A.w.wg_counts, per_node, &a.status->n_lines);
     DRT_LAUNCH(commit_place, per_node, a.nodes, n_nodes, A);
     DRT_LAUNCH(commit_records, (2 * n_inner + kThreads - 1) / kThreads, a.nodes, n_nodes, A, a.status,
                   (float4*)a.recs);
@@ -519,16 +252,9 @@ hipError_t launch_bvh_commit(const BvhCommitArgs& a, hipStream_t st) {
   DRT_LAUNCH(commit_leaf_prims, per_both, a.nodes, n_nodes, a.order, (const float4*)a.prims_raw, n,
                 a.default_material, wide, (float4*)a.leaf_boxes, (float4*)a.prims);
   if (!wide) return hipSuccess;
-  // wide roots sit above the leaves, so there are at most depth - 1 levels of them
-  int levels = (int)a.depth - 1;
-  if (levels > a.max_wide_levels) levels = a.max_wide_levels;
-  if (levels > kMaxLevels - 1) levels = kMaxLevels - 1;
-  const uint32_t level_grid = per_inner < kLevelGridMax ? per_inner : kLevelGridMax;
-  for (int level = 0; level < levels; level++)
-    DRT_LAUNCH(commit_wide_level, level_grid, a.nodes, n_nodes, A, level, a.status);
-  DRT_LAUNCH(commit_wide_count, per_node, n_nodes, A);
-  DRT_LAUNCH(commit_scan, 1, A.wg_counts, per_node, &a.status->n_wide);
-  DRT_LAUNCH(commit_wide_place, per_node, n_nodes, A);
+  const hipError_t e = launch_wide_marks(a.nodes, n_nodes, a.depth, a.max_wide_levels, A.w, &a.status->wide_depth,
+                                         &a.status->n_wide, st);
+  if (e != hipSuccess) return e;
   DRT_LAUNCH(commit_wide_write, per_inner, a.nodes, n_nodes, A, a.status, (uint4*)a.wide_recs);
   return hipSuccess;
 }

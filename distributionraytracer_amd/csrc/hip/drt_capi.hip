@@ -14,6 +14,8 @@
 #include "drt_bvh_ploc.hpp"
 #include "drt_bvh_commit.hpp"
 #include "drt_grid_build.hpp"
+#include "drt_grid_tree_commit.hpp"
+#include "../host/drt_grid_tree_fetch.hpp"
 #include "drt_kernels.hpp"
 #include "drt_layout.hpp"
 #include "../../../include/drt_scene.hpp"
@@ -182,6 +184,11 @@ struct drt_ctx {
   bool has_gv = false;
   DevBuf d_gv_wnodes, d_gv_range, d_gv_prims, d_gv_big;
   uint32_t gv_wroot = 0;
+  // ... committed on the device (drt_build_grid_device with a DRT_GRID_SHADOW_* bit): its status words; while
+  // has_gv and gv_tree_nodes > 0, d_build_nodes / d_build_order hold the binary tree it was collapsed from
+  DevBuf d_gv_status;
+  PinnedBuf h_gv_status;
+  uint32_t gv_tree_nodes = 0;
   // the Grid scene's cell tree (drt_upload_grid_shadow_bvh; drt_layout.hpp CellNodeRecord): 4-ary records of
   // integer cell boxes, the listed primitives in its order with their cell range in q1.w / q2.w, its
   // big-leaf table; ct_root: the root's descriptor
@@ -1032,26 +1039,17 @@ static int raw_prims_to_device(drt_ctx* c, hipStream_t st) {
   return DRT_OK;
 }
 
-// drt_build_bvh_device_ex: the build by either builder, then the host or the device commit
-static int build_bvh_device(drt_ctx* c, drt_bvh_node* nodes_out, uint32_t* order_out, drt_bvh_build_info* info,
-                            bool device_commit, bool ploc) {
-  if (!c) return DRT_E_INVALID;
-  if (!c->has_scene) DRT_FAIL(c, DRT_E_STATE, "upload the scene before building its BVH");
-  if (c->n_prims <= 0) DRT_FAIL(c, DRT_E_INVALID, "a scene without primitives has no BVH");
-  const uint32_t n = (uint32_t)c->n_prims;
-  if (n > kFirstMask) DRT_FAIL(c, DRT_E_UNSUPPORTED, "more than %u objects", kFirstMask);
-  c->has_bvh = c->has_grid = c->has_gv = c->has_ct = false;  // until the commit
+// The build by either builder of a tree of the n resident primitives, as build_bvh_device and the Grid scene's
+// shadow tree (build_grid_shadow_tree) run it: nodes and order in d_build_nodes / d_build_order, pinned host
+// copies of them with `fetch`, the figures in *bi (its commit_ms is the caller's).  commit_scratch: the bytes
+// of d_build a device commit will overlay on the builder's scratch, which is free once the build has ended.
+static int run_bvh_builder(drt_ctx* c, uint32_t n, bool ploc, bool fetch, size_t commit_scratch, drt_bvh_build_info* bi) {
   DRT_HIP(c, hipSetDevice(c->device));
   if (const int rc = ensure_build_events(c)) return rc;
   const size_t max_nodes = 2 * (size_t)n - 1;
   DRT_HIP(c, c->d_prims_raw.ensure(sizeof(drt_prim) * n));
-  // The device commit needs DRT_NODE_LAYOUT=1, DRT_WIDE_ORDER=2 and 4-ary records: otherwise the host commits
-  // (drt_get_bvh_commit_info then reports on_device = 0).
-  device_commit = device_commit && env_int("DRT_NODE_LAYOUT", 1) == 1 && env_int("DRT_WIDE_ORDER", 2) == 2 && kWideK == 4;
-  const bool fetch = !device_commit || nodes_out || order_out;
-  // the commit's scratch overlays the builder's, which is free once the build has ended
   const size_t build_bytes = ploc ? ploc_build_scratch_bytes(n) : bvh_build_scratch_bytes(n);
-  DRT_HIP(c, c->d_build.fit(std::max(build_bytes, device_commit ? bvh_commit_scratch_bytes(n) : 0)));
+  DRT_HIP(c, c->d_build.fit(std::max(build_bytes, commit_scratch)));
   DRT_HIP(c, c->d_build_nodes.fit(sizeof(drt_bvh_node) * max_nodes));
   DRT_HIP(c, c->d_build_order.fit(sizeof(uint32_t) * n));
   DRT_HIP(c, c->d_build_info.ensure(sizeof(uint32_t) * kPlocInfoWords));
@@ -1088,6 +1086,36 @@ static int build_bvh_device(drt_ctx* c, drt_bvh_node* nodes_out, uint32_t* order
     DRT_HIP(c, hipEventElapsedTime(&fetch_ms, c->bev[1], c->bev[2]));
   }
   DRT_HIP(c, hipEventElapsedTime(&build_ms, c->bev[0], c->bev[1]));
+  *bi = drt_bvh_build_info{};
+  bi->n_nodes = n_nodes;
+  bi->n_leaves = n_leaves;
+  bi->depth = depth;
+  bi->build_ms = build_ms;
+  bi->fetch_ms = fetch_ms;
+  bi->builder = ploc ? DRT_BVH_BUILDER_PLOC : DRT_BVH_BUILDER_LBVH;
+  bi->rounds = ploc ? hi[4] : 0u;
+  bi->forced_rounds = ploc ? hi[5] : 0u;
+  return DRT_OK;
+}
+
+// drt_build_bvh_device_ex: the build by either builder, then the host or the device commit
+static int build_bvh_device(drt_ctx* c, drt_bvh_node* nodes_out, uint32_t* order_out, drt_bvh_build_info* info,
+                            bool device_commit, bool ploc) {
+  if (!c) return DRT_E_INVALID;
+  if (!c->has_scene) DRT_FAIL(c, DRT_E_STATE, "upload the scene before building its BVH");
+  if (c->n_prims <= 0) DRT_FAIL(c, DRT_E_INVALID, "a scene without primitives has no BVH");
+  const uint32_t n = (uint32_t)c->n_prims;
+  if (n > kFirstMask) DRT_FAIL(c, DRT_E_UNSUPPORTED, "more than %u objects", kFirstMask);
+  c->has_bvh = c->has_grid = c->has_gv = c->has_ct = false;  // until the commit
+  // The device commit needs DRT_NODE_LAYOUT=1, DRT_WIDE_ORDER=2 and 4-ary records: otherwise the host commits
+  // (drt_get_bvh_commit_info then reports on_device = 0).
+  device_commit = device_commit && env_int("DRT_NODE_LAYOUT", 1) == 1 && env_int("DRT_WIDE_ORDER", 2) == 2 && kWideK == 4;
+  const bool fetch = !device_commit || nodes_out || order_out;
+  drt_bvh_build_info bi{};
+  if (const int rc = run_bvh_builder(c, n, ploc, fetch, device_commit ? bvh_commit_scratch_bytes(n) : 0, &bi)) return rc;
+  const uint32_t n_nodes = bi.n_nodes, n_leaves = bi.n_leaves, depth = bi.depth;
+  drt_bvh_node* hn = (drt_bvh_node*)c->h_build_nodes.p;
+  uint32_t* ho = (uint32_t*)c->h_build_order.p;
   double commit_ms = 0.0;
   if (device_commit) {
     const int rc = commit_bvh_device(c, n, n_nodes, n_leaves, depth, &commit_ms);
@@ -1098,16 +1126,7 @@ static int build_bvh_device(drt_ctx* c, drt_bvh_node* nodes_out, uint32_t* order
     if (rc) return rc;
     commit_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   }
-  drt_bvh_build_info bi{};
-  bi.n_nodes = n_nodes;
-  bi.n_leaves = n_leaves;
-  bi.depth = depth;
-  bi.build_ms = build_ms;
-  bi.fetch_ms = fetch_ms;
   bi.commit_ms = commit_ms;
-  bi.builder = ploc ? DRT_BVH_BUILDER_PLOC : DRT_BVH_BUILDER_LBVH;
-  bi.rounds = ploc ? hi[4] : 0u;
-  bi.forced_rounds = ploc ? hi[5] : 0u;
   c->build_info = bi;
   c->has_build_info = true;
   if (nodes_out) memcpy(nodes_out, hn, sizeof(drt_bvh_node) * n_nodes);
@@ -1428,9 +1447,79 @@ static int commit_grid_device(drt_ctx* c, const GridDims& g, uint32_t n_refs, do
   return DRT_OK;
 }
 
+// The committed device-built grid's shadow tree (DRT_GRID_SHADOW_LBVH / DRT_GRID_SHADOW_PLOC), all of it on the
+// device: a tree of the resident primitives by the chosen builder, then drt_grid_tree_commit.hip writes what
+// drt_upload_grid_shadow_bvh uploads (d_gv_*), from that tree and the cell ranges launch_grid_ranges left in
+// d_gb_ranges, with one 64-B copy back.  *kind: 1 (LBVH) or 2 (PLOC) with the tree resident, 0 without one — a
+// scene the tree does not serve, DRT_GRID_SHADOW_TREE=0, or a tree the commit refused: the Grid walk then
+// answers, which is no error (the host path treats its optional tree the same way).
+static int build_grid_shadow_tree(drt_ctx* c, bool ploc, uint32_t* kind) {
+  *kind = 0u;
+  c->has_gv = false;
+  c->gv_tree_nodes = 0u;
+  const uint32_t n = (uint32_t)c->n_prims;
+  // triangle scenes (the cell tree of other primitives is a host product and off by default); the commit is
+  // build_wide's at DRT_WIDE_ORDER=2 for 4-ary records
+  if (env_int("DRT_GRID_SHADOW_TREE", 1) == 0 || !c->tri_only || n > kFirstMask || kWideK != 4 ||
+      env_int("DRT_WIDE_ORDER", 2) != 2)
+    return DRT_OK;
+  drt_bvh_build_info bi{};
+  if (const int rc = run_bvh_builder(c, n, ploc, false, grid_tree_commit_scratch_bytes(n), &bi)) return rc;
+  for (auto& e : c->cev)
+    if (!e) DRT_HIP(c, hipEventCreate(&e));
+  const size_t n_inner = bi.n_leaves - 1;
+  DRT_HIP(c, c->d_gv_wnodes.ensure(sizeof(WideNodeRecord4) * std::max<size_t>(1, n_inner)));
+  DRT_HIP(c, c->d_gv_range.ensure(sizeof(LeafBoxRecord) * ((size_t)n + 2)));
+  DRT_HIP(c, c->d_gv_prims.ensure(sizeof(PrimRecord) * (size_t)n + kPrimPadBytes));
+  DRT_HIP(c, c->d_gv_big.ensure(sizeof(uint2)));  // a tree with an oversized leaf is refused: no big-leaf table
+  DRT_HIP(c, c->d_gv_status.ensure(sizeof(GridTreeStatus)));
+  DRT_HIP(c, c->h_gv_status.ensure(sizeof(GridTreeStatus)));
+  GridTreeCommitArgs a{};
+  a.nodes = c->d_build_nodes.as<drt_bvh_node>();
+  a.order = c->d_build_order.as<uint32_t>();
+  a.prims_raw = c->d_prims_raw.as<drt_prim>();
+  a.ranges = c->d_gb_ranges.as<int32_t>();
+  a.n_prims = n;
+  a.n_nodes = bi.n_nodes;
+  a.depth = bi.depth;
+  a.default_material = (uint32_t)c->mats.size() - 1u;
+  a.widen_log2 = std::min(-17, env_int("DRT_GRID_TREE_WIDEN_LOG2", -19));  // (drt_upload_grid_shadow_bvh)
+  a.nocert = env_int("DRT_GRID_TREE_NOCERT", 0) != 0;
+  a.max_wide_levels = kWideMaxStack / (kWideK - 1) + 1;
+  a.scratch = c->d_build.p;
+  a.wide_recs = c->d_gv_wnodes.as<WideNodeRecord4>();
+  a.prims = c->d_gv_prims.as<PrimRecord>();
+  a.range_recs = c->d_gv_range.as<LeafBoxRecord>();
+  a.status = c->d_gv_status.as<GridTreeStatus>();
+  hipStream_t st = c->stream;
+  DRT_HIP(c, hipEventRecord(c->cev[0], st));
+  DRT_HIP(c, launch_grid_tree_commit(a, st));
+  DRT_HIP(c, hipEventRecord(c->cev[1], st));
+  const GridTreeStatus* hs = (const GridTreeStatus*)c->h_gv_status.p;
+  DRT_HIP(c, hipMemcpyAsync(c->h_gv_status.p, c->d_gv_status.p, sizeof(GridTreeStatus), hipMemcpyDeviceToHost, st));
+  DRT_HIP(c, hipStreamSynchronize(st));
+  float ms = 0.f;
+  DRT_HIP(c, hipEventElapsedTime(&ms, c->cev[0], c->cev[1]));
+  bi.commit_ms = ms;
+  c->build_info = bi;
+  c->has_build_info = true;
+  if (hs->n_wide > n_inner)
+    DRT_FAIL(c, DRT_E_HIP, "the device commit returned %u wide records for %zu inner nodes", hs->n_wide, n_inner);
+  if (n_inner == 0 || hs->flags != 0u || hs->n_wide == 0 || (kWideK - 1) * (int)hs->wide_depth > kWideMaxStack)
+    return DRT_OK;
+  c->gv_wroot = 0;  // the root is the first mark in node-slot order
+  c->gv_tree_nodes = bi.n_nodes;
+  c->has_gv = true;
+  *kind = ploc ? 2u : 1u;
+  return DRT_OK;
+}
+
 int drt_build_grid_device(drt_ctx* c, float m, int flags, drt_grid_build_info* info) {
   if (!c) return DRT_E_INVALID;
-  if (flags & ~DRT_GRID_COMMIT_DEVICE) DRT_FAIL(c, DRT_E_INVALID, "bad flags %d", flags);
+  const int shadow_bits = flags & (DRT_GRID_SHADOW_LBVH | DRT_GRID_SHADOW_PLOC);
+  if ((flags & ~(DRT_GRID_COMMIT_DEVICE | DRT_GRID_SHADOW_LBVH | DRT_GRID_SHADOW_PLOC)) ||
+      shadow_bits == (DRT_GRID_SHADOW_LBVH | DRT_GRID_SHADOW_PLOC))
+    DRT_FAIL(c, DRT_E_INVALID, "bad flags %d", flags);
   if (!c->has_scene) DRT_FAIL(c, DRT_E_STATE, "upload the scene before building its grid");
   if (c->n_prims <= 0) DRT_FAIL(c, DRT_E_INVALID, "a scene without primitives has no grid to build");
   const uint32_t n = (uint32_t)c->n_prims;
@@ -1515,6 +1604,11 @@ int drt_build_grid_device(drt_ctx* c, float m, int flags, drt_grid_build_info* i
   c->grid_info = gi;
   c->has_grid_info = true;
   c->grid_on_device = true;  // d_cell_start / d_cell_objs hold the builder's lists (the host commit rewrote the same)
+  if (shadow_bits) {
+    const int rc = build_grid_shadow_tree(c, shadow_bits == DRT_GRID_SHADOW_PLOC, &gi.shadow_tree);
+    if (rc) return rc;
+    c->grid_info = gi;
+  }
   if (info) *info = gi;
   return DRT_OK;
 }
@@ -1619,11 +1713,25 @@ int drt_upload_grid_shadow_bvh(drt_ctx* c, const drt_bvh_node* nodes, uint32_t n
   DRT_HIP(c, c->d_gv_big.ensure(sizeof(uint2) * std::max<size_t>(1, big.size())));
   if (!big.empty()) DRT_HIP(c, hipMemcpy(c->d_gv_big.p, big.data(), sizeof(uint2) * big.size(), hipMemcpyHostToDevice));
   c->gv_wroot = wroot;
+  c->gv_tree_nodes = 0u;
   c->has_gv = true;
   return DRT_OK;
 }
 
 }  // extern "C"
+
+int drt::fetch_grid_shadow_tree(drt_ctx* c, drt_bvh_node* nodes, uint32_t* order, uint32_t* n_nodes) {
+  if (!c || !nodes || !order || !n_nodes) return DRT_E_INVALID;
+  if (!c->has_grid || !c->has_gv || c->gv_tree_nodes == 0u)
+    DRT_FAIL(c, DRT_E_STATE, "no device-built shadow tree is resident");
+  DRT_HIP(c, hipSetDevice(c->device));
+  hipStream_t st = c->stream;
+  DRT_HIP(c, hipMemcpyAsync(nodes, c->d_build_nodes.p, sizeof(drt_bvh_node) * c->gv_tree_nodes, hipMemcpyDeviceToHost, st));
+  DRT_HIP(c, hipMemcpyAsync(order, c->d_build_order.p, sizeof(uint32_t) * (size_t)c->n_prims, hipMemcpyDeviceToHost, st));
+  DRT_HIP(c, hipStreamSynchronize(st));
+  *n_nodes = c->gv_tree_nodes;
+  return DRT_OK;
+}
 
 // reference_order: every shadow query walks the reference's binary tree in its visit order
 // (DRT_FRAME_REFERENCE_ORDER: node / leaf / primitive counts equal the reference's)

@@ -5,6 +5,7 @@
 
 #include "../../../include/drt_host.h"
 #include "../../../include/drt_scene.hpp"
+#include "drt_grid_tree_fetch.hpp"
 
 using namespace drt;
 
@@ -362,17 +363,31 @@ int drt_group_scene_upload_device_bvh_ex(drt_group* g, drt_scene* s, int flags) 
 }
 
 int drt_scene_upload_device_grid(drt_ctx* ctx, drt_scene* s, int flags) {
-  if (flags & ~(DRT_GRID_COMMIT_DEVICE | DRT_GRID_NO_INSTALL)) return DRT_E_INVALID;
+  if (flags & ~(DRT_GRID_COMMIT_DEVICE | DRT_GRID_NO_INSTALL | DRT_GRID_SHADOW_LBVH | DRT_GRID_SHADOW_PLOC)) return DRT_E_INVALID;
   int rc = upload_for_device_build(ctx, s, GRID_ACC);
   if (rc) return rc;
   drt_grid_build_info info;
-  rc = drt_build_grid_device(ctx, s->grid.cellFactor(), flags & DRT_GRID_COMMIT_DEVICE, &info);
+  rc = drt_build_grid_device(ctx, s->grid.cellFactor(), flags & ~DRT_GRID_NO_INSTALL, &info);
   if (rc || (flags & DRT_GRID_NO_INSTALL)) return rc;
+  // the tree's nodes come first: the fetch of the lists below leaves the context as it is
+  const size_t n = (size_t)s->scene.getNumObjects();
+  std::vector<drt_bvh_node> nodes(info.shadow_tree ? 2 * n - 1 : 0);
+  std::vector<uint32_t> order(info.shadow_tree ? n : 0);
+  uint32_t n_nodes = 0;
+  if (info.shadow_tree) {
+    rc = fetch_grid_shadow_tree(ctx, nodes.data(), order.data(), &n_nodes);
+    if (rc) return rc;
+  }
   std::vector<int64_t> cs((size_t)info.n_cells + 1);
   std::vector<int32_t> co((size_t)info.n_refs);
   rc = drt_fetch_grid_device(ctx, cs.data(), co.data());
   if (rc) return rc;
-  return drt_scene_set_grid(s, info.dims, info.bmin, info.bmax, cs.data(), (int64_t)cs.size(), co.data(), info.n_refs);
+  rc = drt_scene_set_grid(s, info.dims, info.bmin, info.bmax, cs.data(), (int64_t)cs.size(), co.data(), info.n_refs);
+  if (rc || !info.shadow_tree) return rc;
+  // the host scene's tree for the shadow queries is the one the device walks
+  s->has_gv_bvh = s->gv_bvh.Set(s->scene.objectList(), nodes.data(), n_nodes, order.data(), (uint32_t)n) == DRT_OK;
+  if (!s->has_gv_bvh) s->gv_bvh = BVH();
+  return DRT_OK;
 }
 
 int drt_group_scene_upload_device_grid(drt_group* g, drt_scene* s) {

@@ -269,8 +269,9 @@ int drt_upload_grid(drt_ctx* ctx, const int32_t dims[3], const float bmin[3], co
  * Grid::Build is a deterministic function of the object boxes, and dims, the grown box, cell_start and
  * cell_objs come out bit for bit as drt_scene_build makes them (the cell counts are computed on the host with
  * the same pow, from the world box alone).  Frames and every work count equal the host path's.
- * The Grid scene's shadow tree is not built here: a device-built grid answers shadow queries by the Grid walk,
- * which renders the same frame bit for bit at a lower frame rate, until drt_upload_grid_shadow_bvh adds a tree. */
+ * The Grid scene's shadow tree is built here too when asked for (DRT_GRID_SHADOW_LBVH / DRT_GRID_SHADOW_PLOC
+ * below); without it a device-built grid answers shadow queries by the Grid walk, which renders the same frame
+ * bit for bit at a lower frame rate, until drt_upload_grid_shadow_bvh adds a tree. */
 typedef struct {
   int32_t dims[3];
   float bmin[3], bmax[3]; /* the grown box                                                              */
@@ -281,17 +282,30 @@ typedef struct {
   double fetch_ms;   /* device -> host copy of the lists (0 when they stayed on the device)               */
   double commit_ms;  /* host clock around drt_upload_grid, or device time of the commit kernels           */
   uint32_t on_device; /* 1: committed by the device kernels, 0: by the host (drt_upload_grid)             */
-  uint32_t reserved;
+  uint32_t shadow_tree; /* the shadow tree built with the grid: 0 none (the walk answers), 1 LBVH, 2 PLOC   */
 } drt_grid_build_info;
 #define DRT_GRID_COMMIT_DEVICE 1
+/* (bit 2 is the host wrapper's DRT_GRID_NO_INSTALL, include/drt_host.h) */
+#define DRT_GRID_SHADOW_LBVH 4
+#define DRT_GRID_SHADOW_PLOC 8
 /* After drt_upload_scene: build the grid of the resident primitives on the device with Grid::Build's cell
  * factor m (2 in the reference).  flags = 0: the lists are fetched and committed through drt_upload_grid itself.
  * DRT_GRID_COMMIT_DEVICE: the buffers drt_upload_grid fills (cell lists, inline records, tpos, macro-cell
  * bitmap, scene-order primitives) are written by HIP kernels from the device-resident lists, byte for byte the
  * same, and nothing but status words is copied back; drt_upload_grid_shadow_bvh then answers DRT_E_STATE until a
- * drt_fetch_grid_device has brought the objects' cell ranges to the host.  DRT_E_STATE without a scene,
- * DRT_E_INVALID for a scene without primitives or other flag bits, DRT_E_UNSUPPORTED for an object box with a
- * non-finite component, 2^31 cells or references or more; DRT_E_OOM / DRT_E_HIP as elsewhere. */
+ * drt_fetch_grid_device has brought the objects' cell ranges to the host.
+ * DRT_GRID_SHADOW_LBVH or DRT_GRID_SHADOW_PLOC (one of them, with either commit): once the grid is committed,
+ * the LBVH or the PLOC builder (drt_build_bvh_device_ex) builds a tree of the resident primitives and HIP
+ * kernels (csrc/hip/drt_grid_tree_commit.hip) commit it as the Grid scene's shadow tree — what
+ * drt_upload_grid_shadow_bvh uploads for a triangle scene, from the cell ranges the grid build left on the
+ * device, with one 64-B status read.  info->shadow_tree says which tree is resident; drt_get_bvh_build_info
+ * then reports that tree's figures, its commit_ms the device time of the commit kernels.  No tree
+ * (shadow_tree = 0, the Grid walk answers, no error) for a scene with other primitives than triangles, under
+ * DRT_GRID_SHADOW_TREE=0, or when the tree has a leaf root, a record that does not quantise or too many
+ * levels for the shadow stack.  DRT_E_STATE without a scene,
+ * DRT_E_INVALID for a scene without primitives, other flag bits or both shadow bits, DRT_E_UNSUPPORTED for an
+ * object box with a non-finite component, 2^31 cells or references or more; DRT_E_OOM / DRT_E_HIP as
+ * elsewhere. */
 int drt_build_grid_device(drt_ctx* ctx, float m, int flags, drt_grid_build_info* info);
 /* The lists of the resident device-built grid: cell_start (n_cells + 1) and cell_objs (n_refs) as
  * drt_upload_grid takes them, sizes from the info.  Either may be NULL.  DRT_E_STATE unless the resident grid

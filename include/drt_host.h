@@ -115,8 +115,11 @@ int drt_scene_set_grid(drt_scene* s, const int32_t dims[3], const float bmin[3],
  * (include/drt.h) with the scene's cell factor, then drt_fetch_grid_device and drt_scene_set_grid, so the host
  * scene holds the grid the device walks.  DRT_GRID_COMMIT_DEVICE (include/drt.h) commits on the device;
  * DRT_GRID_NO_INSTALL skips the fetch and the install (the host scene is then not marked built by this call).
- * No shadow tree is uploaded: shadow queries take the Grid walk.  The group form builds once, on rank 0,
- * installs, and uploads to the other ranks by the host path. */
+ * DRT_GRID_SHADOW_LBVH / DRT_GRID_SHADOW_PLOC (include/drt.h) are passed on: the shadow tree is built and
+ * committed on the device, and an installing call also stores the binary tree behind it in the host scene, so
+ * that a later drt_scene_upload commits the same tree through drt_upload_grid_shadow_bvh.  Without them no
+ * shadow tree is uploaded: shadow queries take the Grid walk.  The group form builds once, on rank 0,
+ * installs, and uploads to the other ranks by the host path; it takes no shadow bits. */
 enum { DRT_GRID_NO_INSTALL = 2 };
 int drt_scene_upload_device_grid(drt_ctx* ctx, drt_scene* s, int flags);
 int drt_group_scene_upload_device_grid(drt_group* g, drt_scene* s);

@@ -14,6 +14,12 @@ Two JSON lines, every figure as median [min, max]:
           events) and Mrays/s = (closest + shadow traversals of a stats frame) / median ms.
 
   python tools/grid_build_ab.py [--rounds 10] [--tris 1000000] > profiles/gpu_grid_build.jsonl
+
+--shadow-trees adds two device arms whose upload also builds and commits the Grid scene's shadow tree on the
+device (shadow_tree="device": LBVH, "ploc": PLOC; commit="device"): their builds record carries the tree's
+builder and commit times (drt_bvh_build_info, HIP events), their frames answer shadow queries on that tree.
+
+  python tools/grid_build_ab.py --shadow-trees --rounds 5 > profiles/gpu_grid_shadow_build.jsonl
 """
 import argparse
 import json
@@ -41,6 +47,7 @@ def main():
     ap.add_argument("--tris", type=int, default=1_000_000)
     ap.add_argument("--res", type=int, default=512)
     ap.add_argument("--spp", type=int, default=64)
+    ap.add_argument("--shadow-trees", action="store_true")
     args = ap.parse_args()
     tris = bench.synthetic_triangles(args.tris)
 
@@ -50,9 +57,12 @@ def main():
         return s
 
     dev_arms = {"device": {}, "dcommit": {"commit": "device"}, "dcommit_noinstall": {"commit": "device", "install": False}}
+    tree_arms = {"dcommit_lbvh": "device", "dcommit_ploc": "ploc"} if args.shadow_trees else {}
+    dev_arms.update({a: {"commit": "device", "shadow_tree": t} for a, t in tree_arms.items()})
     ctx = {a: drt.Renderer(0) for a in ("host", *dev_arms)}
     rows = {"host_grid_build_ms": [], "host_shadow_bvh_build_ms": [], "host_upload_wall_ms": []}
     rows.update({f"{a}_{k}_ms": [] for a in dev_arms for k in ("build", "fetch", "commit", "upload_wall")})
+    rows.update({f"{a}_shadow_{k}_ms": [] for a in tree_arms for k in ("build", "commit")})
     info = None
     for rnd in range(args.rounds + 1):  # round 0 warms every arm up (code objects, allocations, pinned buffers)
         s = fresh()
@@ -77,6 +87,11 @@ def main():
             for k in ("build", "fetch", "commit"):
                 rows[f"{a}_{k}_ms"].append(info[f"{k}_ms"])
             rows[f"{a}_upload_wall_ms"].append((t4 - t3) * 1e3)
+            if a in tree_arms:
+                assert info["shadow_tree"] == (1 if tree_arms[a] == "device" else 2), info
+                tree = ctx[a].bvh_build_info()
+                rows[f"{a}_shadow_build_ms"].append(tree["build_ms"])
+                rows[f"{a}_shadow_commit_ms"].append(tree["commit_ms"])
     out = {"record": "builds", "objects": int(s.info().n_objects), "rounds": args.rounds, "dims": info["dims"],
            "n_cells": info["n_cells"], "n_refs": info["n_refs"]}
     out.update({k: spread(v) for k, v in rows.items()})
@@ -86,7 +101,7 @@ def main():
             out["host_upload_wall_ms"]["median"] / out[f"{a}_upload_wall_ms"]["median"], 1)
     print(json.dumps(out), flush=True)
 
-    arms = ("host", "dcommit")
+    arms = ("host", "dcommit", *tree_arms)
     rays, ms = {}, {a: [] for a in arms}
     for a in arms:
         ctx[a].render(seed=7, stats=True)
@@ -98,11 +113,13 @@ def main():
             if rnd >= 2:
                 ms[a].append(float(ctx[a].frame_times(1)[1][-1]))
     out = {"record": "frames", "res": args.res, "spp": args.spp, "rounds": args.rounds,
-           "shadow_queries": {"host": "shadow tree", "dcommit": "Grid walk"}}
+           "shadow_queries": {"host": "shadow tree", "dcommit": "Grid walk",
+                              **{a: f"device-built shadow tree ({t})" for a, t in tree_arms.items()}}}
     for a in arms:
         m = spread(ms[a])
         out[a] = {"frame_ms": m, "mrays_s": round(rays[a] / m["median"] / 1e3, 1), "rays": int(rays[a])}
-    out["dcommit_over_host_frame_rate"] = round(out["host"]["frame_ms"]["median"] / out["dcommit"]["frame_ms"]["median"], 3)
+    for a in arms[1:]:
+        out[f"{a}_over_host_frame_rate"] = round(out["host"]["frame_ms"]["median"] / out[a]["frame_ms"]["median"], 3)
     print(json.dumps(out), flush=True)
     for r in ctx.values():
         r.close()
