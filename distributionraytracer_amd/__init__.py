@@ -293,17 +293,21 @@ class Renderer:
         no tree is built: shadow queries take the Grid walk, which renders the same frame at a lower rate.
         build="ploc" (BVH scenes only): as build="device" with the PLOC builder (drt_build_bvh_device_ex,
         csrc/hip/drt_bvh_ploc.hip) in place of the LBVH: more kernel rounds to build, a tree of lower
-        surface-area cost (README.md, Use); commit and install as with build="device"."""
-        if build not in ("host", "device", "ploc"):
-            raise ValueError(f"build must be 'host', 'device' or 'ploc', not {build!r}")
+        surface-area cost (README.md, Use); commit and install as with build="device".
+        build="binned" (BVH scenes only): the binned-SAH builder (csrc/hip/drt_bvh_binned.hip), which builds
+        the tree of build="host" itself on the device, node for node, so it renders at the host tree's rate
+        and counts; commit and install as with build="device".  A tree with a leaf of 31 objects or more
+        (degenerate scenes) is committed by the host even with commit="device": bvh_commit_info() says so."""
+        if build not in ("host", "device", "ploc", "binned"):
+            raise ValueError(f"build must be 'host', 'device', 'ploc' or 'binned', not {build!r}")
         if commit not in ("host", "device"):
             raise ValueError(f"commit must be 'host' or 'device', not {commit!r}")
         if build == "host" and (commit == "device" or not install):
-            raise ValueError("commit='device' and install=False need build='device' or 'ploc'")
+            raise ValueError("commit='device' and install=False need build='device', 'ploc' or 'binned'")
         if shadow_tree not in (None, "device", "ploc"):
             raise ValueError(f"shadow_tree must be None, 'device' or 'ploc', not {shadow_tree!r}")
-        if build == "ploc" and scene.info().accel == ACCEL["grid"]:
-            raise ValueError("build='ploc' is a BVH builder: a Grid scene has one device builder, build='device'")
+        if build in ("ploc", "binned") and scene.info().accel == ACCEL["grid"]:
+            raise ValueError(f"build={build!r} is a BVH builder: a Grid scene has one device builder, build='device'")
         if shadow_tree is not None and (build == "host" or scene.info().accel != ACCEL["grid"]):
             raise ValueError("shadow_tree needs a Grid scene and build='device'")
         if build == "host":
@@ -317,7 +321,7 @@ class Renderer:
             check(_lib.load().drt_scene_upload_device_bvh(self.h, scene.h), self.h, "drt_scene_upload_device_bvh")
         else:
             flags = ((_lib.BVH_COMMIT_DEVICE if commit == "device" else 0) | (0 if install else _lib.BVH_NO_INSTALL) |
-                     (_lib.BVH_BUILDER_PLOC_FLAG if build == "ploc" else 0))
+                     {"device": 0, "ploc": _lib.BVH_BUILDER_PLOC_FLAG, "binned": _lib.BVH_BUILDER_BINNED_FLAG}[build])
             check(_lib.load().drt_scene_upload_device_bvh_ex(self.h, scene.h, flags), self.h,
                   "drt_scene_upload_device_bvh_ex")
         self.scene = scene
@@ -341,8 +345,9 @@ class Renderer:
                 for k, v in out.items()}
 
     def bvh_build_info(self):
-        """drt_bvh_build_info of the last build="device" or "ploc" upload: nodes, leaves, depth, the build /
-        fetch / commit times in ms, the builder (0 LBVH, 1 PLOC) and PLOC's search and forced round counts."""
+        """drt_bvh_build_info of the last build="device", "ploc" or "binned" upload: nodes, leaves, depth, the
+        build / fetch / commit times in ms, the builder (0 LBVH, 1 PLOC, 2 binned SAH), PLOC's search and forced
+        round counts, and in `rounds` the binned builder's level-wise rounds."""
         i = _lib.DrtBvhBuildInfo()
         check(_lib.load().drt_get_bvh_build_info(self.h, C.byref(i)), self.h, "drt_get_bvh_build_info")
         return {n: (float(getattr(i, n)) if n.endswith("_ms") else int(getattr(i, n))) for n, _ in i._fields_}
@@ -540,15 +545,17 @@ class RendererGroup:
 
     def upload(self, scene: Scene, build="host"):
         """build="device": the tree is built once, on the first device (Renderer.upload), and the same
-        arrays are committed on every device.  build="ploc": the same with the PLOC builder (BVH scenes).
+        arrays are committed on every device.  build="ploc" or "binned": the same with the PLOC or the
+        binned-SAH builder (BVH scenes).
         Renderer.upload's shadow_tree (a Grid scene's shadow tree built on the device) is not offered here:
         a group's device-built grid answers shadow queries by the Grid walk."""
-        if build not in ("host", "device", "ploc"):
-            raise ValueError(f"build must be 'host', 'device' or 'ploc', not {build!r}")
-        if build == "ploc" and scene.info().accel == ACCEL["grid"]:
-            raise ValueError("build='ploc' is a BVH builder: a Grid scene has one device builder, build='device'")
-        if build == "ploc":
-            self._check(_lib.load().drt_group_scene_upload_device_bvh_ex(self.h, scene.h, _lib.BVH_BUILDER_PLOC_FLAG),
+        if build not in ("host", "device", "ploc", "binned"):
+            raise ValueError(f"build must be 'host', 'device', 'ploc' or 'binned', not {build!r}")
+        if build in ("ploc", "binned") and scene.info().accel == ACCEL["grid"]:
+            raise ValueError(f"build={build!r} is a BVH builder: a Grid scene has one device builder, build='device'")
+        if build in ("ploc", "binned"):
+            flag = _lib.BVH_BUILDER_PLOC_FLAG if build == "ploc" else _lib.BVH_BUILDER_BINNED_FLAG
+            self._check(_lib.load().drt_group_scene_upload_device_bvh_ex(self.h, scene.h, flag),
                         "drt_group_scene_upload_device_bvh_ex")
         elif build == "device" and scene.info().accel == ACCEL["grid"]:
             self._check(_lib.load().drt_group_scene_upload_device_grid(self.h, scene.h),

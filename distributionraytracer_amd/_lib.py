@@ -116,6 +116,7 @@ class DrtBvhCommitInfo(C.Structure):
 
 
 BVH_COMMIT_DEVICE, BVH_NO_INSTALL, BVH_BUILDER_PLOC_FLAG = 1, 2, 4  # drt_scene_upload_device_bvh_ex flags (drt_host.h)
+BVH_BUILDER_BINNED_FLAG = 8
 GRID_COMMIT_DEVICE, GRID_NO_INSTALL = 1, 2  # drt_scene_upload_device_grid flags (include/drt.h, drt_host.h)
 GRID_SHADOW_LBVH, GRID_SHADOW_PLOC = 4, 8   # ... and the shadow tree built with the grid (include/drt.h)
 

@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "drt_bvh_build.hpp"
+#include "drt_bvh_binned.hpp"
 #include "drt_bvh_ploc.hpp"
 #include "drt_bvh_commit.hpp"
 #include "drt_grid_build.hpp"
@@ -1039,16 +1040,21 @@ static int raw_prims_to_device(drt_ctx* c, hipStream_t st) {
   return DRT_OK;
 }
 
-// The build by either builder of a tree of the n resident primitives, as build_bvh_device and the Grid scene's
-// shadow tree (build_grid_shadow_tree) run it: nodes and order in d_build_nodes / d_build_order, pinned host
-// copies of them with `fetch`, the figures in *bi (its commit_ms is the caller's).  commit_scratch: the bytes
+// The build by one of the builders of a tree of the n resident primitives, as build_bvh_device and the Grid
+// scene's shadow tree (build_grid_shadow_tree) run it: nodes and order in d_build_nodes / d_build_order, pinned
+// host copies of them with `fetch`, the figures in *bi (its commit_ms is the caller's).  commit_scratch: the bytes
 // of d_build a device commit will overlay on the builder's scratch, which is free once the build has ended.
-static int run_bvh_builder(drt_ctx* c, uint32_t n, bool ploc, bool fetch, size_t commit_scratch, drt_bvh_build_info* bi) {
+// *big_leaf (if given): the tree has a leaf the device commit's descriptors cannot hold (kBigLeaf objects or more,
+// the binned builder's fallback leaves); it is then fetched whatever `fetch` says, for the host to commit.
+static int run_bvh_builder(drt_ctx* c, uint32_t n, int builder, bool fetch, size_t commit_scratch, drt_bvh_build_info* bi,
+                           bool* big_leaf = nullptr) {
+  const bool ploc = builder == DRT_BVH_BUILDER_PLOC, binned = builder == DRT_BVH_BUILDER_BINNED;
+  static_assert(kBinnedInfoWords == kPlocInfoWords && kBinnedHostWords >= 1, "one info block serves both");
   DRT_HIP(c, hipSetDevice(c->device));
   if (const int rc = ensure_build_events(c)) return rc;
   const size_t max_nodes = 2 * (size_t)n - 1;
   DRT_HIP(c, c->d_prims_raw.ensure(sizeof(drt_prim) * n));
-  const size_t build_bytes = ploc ? ploc_build_scratch_bytes(n) : bvh_build_scratch_bytes(n);
+  const size_t build_bytes = binned ? binned_build_scratch_bytes(n) : ploc ? ploc_build_scratch_bytes(n) : bvh_build_scratch_bytes(n);
   DRT_HIP(c, c->d_build.fit(std::max(build_bytes, commit_scratch)));
   DRT_HIP(c, c->d_build_nodes.fit(sizeof(drt_bvh_node) * max_nodes));
   DRT_HIP(c, c->d_build_order.fit(sizeof(uint32_t) * n));
@@ -1057,12 +1063,16 @@ static int run_bvh_builder(drt_ctx* c, uint32_t n, bool ploc, bool fetch, size_t
     DRT_HIP(c, c->h_build_nodes.ensure(sizeof(drt_bvh_node) * max_nodes));
     DRT_HIP(c, c->h_build_order.ensure(sizeof(uint32_t) * n));
   }
-  DRT_HIP(c, c->h_build_info.ensure(sizeof(uint32_t) * (kPlocInfoWords + 1)));  // + PLOC's live count
+  DRT_HIP(c, c->h_build_info.ensure(sizeof(uint32_t) * (kPlocInfoWords + kBinnedHostWords)));  // + the builders' counts
   hipStream_t st = c->stream;
   uint32_t* hi = (uint32_t*)c->h_build_info.p;
   DRT_HIP(c, hipEventRecord(c->bev[0], st));
   if (const int rc = raw_prims_to_device(c, st)) return rc;
-  if (ploc) {
+  if (binned) {
+    DRT_HIP(c, launch_binned_build(c->d_prims_raw.as<drt_prim>(), n, c->d_build.p, c->d_build_nodes.as<drt_bvh_node>(),
+                                   c->d_build_order.as<uint32_t>(), c->d_build_info.as<uint32_t>(), hi + kPlocInfoWords, st));
+    if (hi[kPlocInfoWords] != 0u) DRT_FAIL(c, DRT_E_INVALID, "the binned tree is deeper than %d levels", kBinnedMaxRounds);
+  } else if (ploc) {
     DRT_HIP(c, launch_ploc_build(c->d_prims_raw.as<drt_prim>(), n, c->d_build.p, c->d_build_nodes.as<drt_bvh_node>(),
                                  c->d_build_order.as<uint32_t>(), c->d_build_info.as<uint32_t>(), hi + kPlocInfoWords, st));
   } else {
@@ -1070,11 +1080,20 @@ static int run_bvh_builder(drt_ctx* c, uint32_t n, bool ploc, bool fetch, size_t
                                 c->d_build_order.as<uint32_t>(), c->d_build_info.as<uint32_t>(), st));
   }
   DRT_HIP(c, hipEventRecord(c->bev[1], st));
-  DRT_HIP(c, hipMemcpyAsync(hi, c->d_build_info.p, sizeof(uint32_t) * (ploc ? kPlocInfoWords : 4), hipMemcpyDeviceToHost, st));
+  DRT_HIP(c, hipMemcpyAsync(hi, c->d_build_info.p, sizeof(uint32_t) * (ploc || binned ? kPlocInfoWords : 4), hipMemcpyDeviceToHost, st));
   DRT_HIP(c, hipStreamSynchronize(st));
   const uint32_t n_nodes = hi[0], n_leaves = hi[1], depth = hi[2];
   if (n_nodes == 0 || n_nodes > max_nodes || n_nodes != 2 * n_leaves - 1)
     DRT_FAIL(c, DRT_E_HIP, "the device build returned %u nodes, %u leaves for %u objects", n_nodes, n_leaves, n);
+  if (binned && depth >= 96u) DRT_FAIL(c, DRT_E_INVALID, "the binned tree has %u levels: above the traversal stack's 95", depth);
+  if (binned && hi[6] >= kBigLeaf) {
+    if (big_leaf) *big_leaf = true;
+    if (!fetch) {  // the one case that learns after the build that it fetches
+      DRT_HIP(c, c->h_build_nodes.ensure(sizeof(drt_bvh_node) * max_nodes));
+      DRT_HIP(c, c->h_build_order.ensure(sizeof(uint32_t) * n));
+      fetch = true;
+    }
+  }
   drt_bvh_node* hn = (drt_bvh_node*)c->h_build_nodes.p;
   uint32_t* ho = (uint32_t*)c->h_build_order.p;
   float build_ms = 0.f, fetch_ms = 0.f;
@@ -1092,15 +1111,15 @@ static int run_bvh_builder(drt_ctx* c, uint32_t n, bool ploc, bool fetch, size_t
   bi->depth = depth;
   bi->build_ms = build_ms;
   bi->fetch_ms = fetch_ms;
-  bi->builder = ploc ? DRT_BVH_BUILDER_PLOC : DRT_BVH_BUILDER_LBVH;
-  bi->rounds = ploc ? hi[4] : 0u;
+  bi->builder = (uint32_t)builder;
+  bi->rounds = ploc || binned ? hi[4] : 0u;
   bi->forced_rounds = ploc ? hi[5] : 0u;
   return DRT_OK;
 }
 
-// drt_build_bvh_device_ex: the build by either builder, then the host or the device commit
+// drt_build_bvh_device_ex: the build by the chosen builder, then the host or the device commit
 static int build_bvh_device(drt_ctx* c, drt_bvh_node* nodes_out, uint32_t* order_out, drt_bvh_build_info* info,
-                            bool device_commit, bool ploc) {
+                            bool device_commit, int builder) {
   if (!c) return DRT_E_INVALID;
   if (!c->has_scene) DRT_FAIL(c, DRT_E_STATE, "upload the scene before building its BVH");
   if (c->n_prims <= 0) DRT_FAIL(c, DRT_E_INVALID, "a scene without primitives has no BVH");
@@ -1112,7 +1131,9 @@ static int build_bvh_device(drt_ctx* c, drt_bvh_node* nodes_out, uint32_t* order
   device_commit = device_commit && env_int("DRT_NODE_LAYOUT", 1) == 1 && env_int("DRT_WIDE_ORDER", 2) == 2 && kWideK == 4;
   const bool fetch = !device_commit || nodes_out || order_out;
   drt_bvh_build_info bi{};
-  if (const int rc = run_bvh_builder(c, n, ploc, fetch, device_commit ? bvh_commit_scratch_bytes(n) : 0, &bi)) return rc;
+  bool big_leaf = false;
+  if (const int rc = run_bvh_builder(c, n, builder, fetch, device_commit ? bvh_commit_scratch_bytes(n) : 0, &bi, &big_leaf)) return rc;
+  if (big_leaf) device_commit = false;  // the host commit keeps such leaves in its table of big leaves
   const uint32_t n_nodes = bi.n_nodes, n_leaves = bi.n_leaves, depth = bi.depth;
   drt_bvh_node* hn = (drt_bvh_node*)c->h_build_nodes.p;
   uint32_t* ho = (uint32_t*)c->h_build_order.p;
@@ -1146,10 +1167,9 @@ int drt_build_bvh_device_commit(drt_ctx* c, drt_bvh_node* nodes_out, uint32_t* o
 int drt_build_bvh_device_ex(drt_ctx* c, int builder, int flags, drt_bvh_node* nodes_out, uint32_t* order_out,
                             drt_bvh_build_info* info) {
   if (!c) return DRT_E_INVALID;
-  if (builder != DRT_BVH_BUILDER_LBVH && builder != DRT_BVH_BUILDER_PLOC) DRT_FAIL(c, DRT_E_INVALID, "bad builder %d", builder);
+  if (builder != DRT_BVH_BUILDER_LBVH && builder != DRT_BVH_BUILDER_PLOC && builder != DRT_BVH_BUILDER_BINNED) DRT_FAIL(c, DRT_E_INVALID, "bad builder %d", builder);
   if (flags & ~DRT_BVH_EX_COMMIT_DEVICE) DRT_FAIL(c, DRT_E_INVALID, "bad flags %d", flags);
-  return build_bvh_device(c, nodes_out, order_out, info, (flags & DRT_BVH_EX_COMMIT_DEVICE) != 0,
-                          builder == DRT_BVH_BUILDER_PLOC);
+  return build_bvh_device(c, nodes_out, order_out, info, (flags & DRT_BVH_EX_COMMIT_DEVICE) != 0, builder);
 }
 
 int drt_get_bvh_commit_info(const drt_ctx* c, drt_bvh_commit_info* info) {
@@ -1464,7 +1484,8 @@ static int build_grid_shadow_tree(drt_ctx* c, bool ploc, uint32_t* kind) {
       env_int("DRT_WIDE_ORDER", 2) != 2)
     return DRT_OK;
   drt_bvh_build_info bi{};
-  if (const int rc = run_bvh_builder(c, n, ploc, false, grid_tree_commit_scratch_bytes(n), &bi)) return rc;
+  if (const int rc = run_bvh_builder(c, n, ploc ? DRT_BVH_BUILDER_PLOC : DRT_BVH_BUILDER_LBVH, false, grid_tree_commit_scratch_bytes(n), &bi))
+    return rc;
   for (auto& e : c->cev)
     if (!e) DRT_HIP(c, hipEventCreate(&e));
   const size_t n_inner = bi.n_leaves - 1;

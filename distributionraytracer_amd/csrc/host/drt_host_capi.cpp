@@ -316,7 +316,8 @@ int drt_scene_upload_device_bvh(drt_ctx* ctx, drt_scene* s) {
 }
 
 int drt_scene_upload_device_bvh_ex(drt_ctx* ctx, drt_scene* s, int flags) {
-  if (flags & ~(DRT_BVH_COMMIT_DEVICE | DRT_BVH_NO_INSTALL | DRT_BVH_BUILDER_PLOC_FLAG)) return DRT_E_INVALID;
+  const int builders = DRT_BVH_BUILDER_PLOC_FLAG | DRT_BVH_BUILDER_BINNED_FLAG;
+  if ((flags & ~(DRT_BVH_COMMIT_DEVICE | DRT_BVH_NO_INSTALL | builders)) || (flags & builders) == builders) return DRT_E_INVALID;
   if (flags == 0) return drt_scene_upload_device_bvh(ctx, s);
   int rc = upload_for_device_build(ctx, s);
   if (rc) return rc;
@@ -328,7 +329,10 @@ int drt_scene_upload_device_bvh_ex(drt_ctx* ctx, drt_scene* s, int flags) {
   drt_bvh_node* np = install ? nodes.data() : nullptr;
   uint32_t* op = install ? order.data() : nullptr;
   drt_bvh_build_info info;
-  rc = drt_build_bvh_device_ex(ctx, (flags & DRT_BVH_BUILDER_PLOC_FLAG) ? DRT_BVH_BUILDER_PLOC : DRT_BVH_BUILDER_LBVH,
+  const int builder = (flags & DRT_BVH_BUILDER_PLOC_FLAG)     ? DRT_BVH_BUILDER_PLOC
+                      : (flags & DRT_BVH_BUILDER_BINNED_FLAG) ? DRT_BVH_BUILDER_BINNED
+                                                              : DRT_BVH_BUILDER_LBVH;
+  rc = drt_build_bvh_device_ex(ctx, builder,
                                (flags & DRT_BVH_COMMIT_DEVICE) ? DRT_BVH_EX_COMMIT_DEVICE : 0, np, op, &info);
   if (rc || !install) return rc;
   return drt_scene_set_bvh(s, np, info.n_nodes, op, (uint32_t)n);
@@ -337,7 +341,7 @@ int drt_scene_upload_device_bvh_ex(drt_ctx* ctx, drt_scene* s, int flags) {
 int drt_group_scene_upload_device_bvh(drt_group* g, drt_scene* s) { return drt_group_scene_upload_device_bvh_ex(g, s, 0); }
 
 int drt_group_scene_upload_device_bvh_ex(drt_group* g, drt_scene* s, int flags) {
-  if (!g || !s || (flags & ~DRT_BVH_BUILDER_PLOC_FLAG)) return DRT_E_INVALID;
+  if (!g || !s || (flags & ~(DRT_BVH_BUILDER_PLOC_FLAG | DRT_BVH_BUILDER_BINNED_FLAG))) return DRT_E_INVALID;
   int rc = drt_scene_upload_device_bvh_ex(drt_group_ctx(g, 0), s, flags);  // built once, on rank 0
   if (rc) return rc;
   const auto& nd = s->bvh.nodeList();

@@ -218,8 +218,8 @@ typedef struct {
                         and that copy is inside this time                                             */
   double fetch_ms;   /* device -> host copy of nodes and order                  */
   double commit_ms;  /* host clock around the existing drt_upload_bvh commit    */
-  uint32_t builder;        /* DRT_BVH_BUILDER_LBVH or DRT_BVH_BUILDER_PLOC                              */
-  uint32_t rounds;         /* PLOC: search rounds run (0 for the LBVH)                                   */
+  uint32_t builder;        /* DRT_BVH_BUILDER_LBVH, DRT_BVH_BUILDER_PLOC or DRT_BVH_BUILDER_BINNED       */
+  uint32_t rounds;         /* PLOC: search rounds run; binned: level-wise rounds run (0 for the LBVH)    */
   uint32_t forced_rounds;  /* PLOC: rounds after them that paired neighbours whatever their boxes        */
 } drt_bvh_build_info;
 
@@ -228,17 +228,28 @@ typedef struct {
  * NULL; otherwise they receive the tree.  DRT_E_STATE without a scene, DRT_E_INVALID for a scene without
  * primitives, DRT_E_OOM / DRT_E_HIP as elsewhere. */
 int drt_build_bvh_device(drt_ctx* ctx, drt_bvh_node* nodes_out, uint32_t* order_out, drt_bvh_build_info* info);
-/* The same with the builder chosen.  DRT_BVH_BUILDER_PLOC (csrc/hip/drt_bvh_ploc.hip) is parallel locally-ordered
+/* The same with the builder chosen, one of three.  DRT_BVH_BUILDER_PLOC (csrc/hip/drt_bvh_ploc.hip) is parallel locally-ordered
  * clustering (Meister and Bittner 2018) over the LBVH's Morton order: every round each cluster looks 8 clusters
  * to each side for the one whose union box has the least surface, mutual nearest neighbours merge, and the
  * cluster array is compacted; after 64 such rounds neighbours are paired whatever their boxes, so the depth is
  * at most 91.  The tree has the LBVH's shape rules and goes through the same commits; it costs more rounds of
  * kernels to build and has a lower surface-area cost (README.md, Use, for the measured figures).  flags: 0 or
  * DRT_BVH_EX_COMMIT_DEVICE (the commit of drt_build_bvh_device_commit).  drt_build_bvh_device and
- * drt_build_bvh_device_commit are this call with DRT_BVH_BUILDER_LBVH.  DRT_E_INVALID for another builder or
- * flag. */
+ * drt_build_bvh_device_commit are this call with DRT_BVH_BUILDER_LBVH.
+ * DRT_BVH_BUILDER_BINNED (csrc/hip/drt_bvh_binned.hip) builds the reference's binned-SAH tree itself, the one
+ * drt_scene_build builds on the host: leaf, index, n_objs and every box equal it bit for bit, and every leaf
+ * holds the same objects, in ascending centroid on the leaf's sort axis with equal keys in scene order (the
+ * host's sequence wherever a leaf's keys are distinct).  One exception to the boxes' bits: where the objects of
+ * one bucket have both +0 and -0 as a bound, the host keeps the zero its sort met first and this builder -0 as a
+ * minimum, +0 as a maximum.  Nodes above 64 objects are split level by level
+ * (info->rounds rounds, forced_rounds 0), smaller ones by one wave each.  The reference's tree may hold leaves of
+ * any size: with DRT_BVH_EX_COMMIT_DEVICE a tree with a leaf of 31 objects or more is committed by the host
+ * (drt_get_bvh_commit_info says so), every other one on the device.  DRT_E_INVALID for a tree deeper than the 96
+ * levels drt_upload_bvh takes.
+ * DRT_E_INVALID for any other builder or flag. */
 #define DRT_BVH_BUILDER_LBVH 0
 #define DRT_BVH_BUILDER_PLOC 1
+#define DRT_BVH_BUILDER_BINNED 2
 #define DRT_BVH_EX_COMMIT_DEVICE 1
 int drt_build_bvh_device_ex(drt_ctx* ctx, int builder, int flags, drt_bvh_node* nodes_out, uint32_t* order_out,
                             drt_bvh_build_info* info);

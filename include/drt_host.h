@@ -99,9 +99,11 @@ int drt_group_scene_upload_device_bvh(drt_group* g, drt_scene* s);
  * host scene is not marked built by this call, so drt_scene_trace_cpu and drt_scene_bvh_export behave as on
  * an unbuilt scene (they build, or keep, the host's own tree, which is not the one the device walks).  Other
  * DRT_BVH_BUILDER_PLOC_FLAG builds with the PLOC builder (drt_build_bvh_device_ex, DRT_BVH_BUILDER_PLOC) instead
- * of the LBVH, and composes with both.  Other flag bits are DRT_E_INVALID.  The group form keeps the host
- * commit and takes DRT_BVH_BUILDER_PLOC_FLAG alone. */
-enum { DRT_BVH_COMMIT_DEVICE = 1, DRT_BVH_NO_INSTALL = 2, DRT_BVH_BUILDER_PLOC_FLAG = 4 };
+ * of the LBVH, and composes with both; DRT_BVH_BUILDER_BINNED_FLAG likewise with the binned-SAH builder
+ * (DRT_BVH_BUILDER_BINNED: the tree drt_scene_build builds, built on the device).  The two builder flags exclude
+ * each other.  Other flag bits are DRT_E_INVALID.  The group form keeps the host commit and takes one builder
+ * flag alone. */
+enum { DRT_BVH_COMMIT_DEVICE = 1, DRT_BVH_NO_INSTALL = 2, DRT_BVH_BUILDER_PLOC_FLAG = 4, DRT_BVH_BUILDER_BINNED_FLAG = 8 };
 int drt_scene_upload_device_bvh_ex(drt_ctx* ctx, drt_scene* s, int flags);
 int drt_group_scene_upload_device_bvh_ex(drt_group* g, drt_scene* s, int flags);
 /* Install a caller's cell lists as a Grid scene's grid (the inverse of drt_scene_grid_export*): dims, box, CSR

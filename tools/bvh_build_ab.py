@@ -4,7 +4,9 @@ the host's binned-SAH build (drt_scene_build, tree-identical to the reference) a
 (drt_build_bvh_device_commit) with and without installing the tree in the host scene; the headline frame on
 each committed tree.  The PLOC builder (drt_build_bvh_device_ex, build="ploc") is two more arms, ploc (host commit)
 and ploc_dcommit (device commit), with its round count, and the builds line carries each tree's surface-area
-cost: (sum of inner box surfaces + sum of leaf box surfaces x objects) / the root's surface.
+cost: (sum of inner box surfaces + sum of leaf box surfaces x objects) / the root's surface.  The binned-SAH
+builder (build="binned", the host's tree built on the device) is three more arms: binned, binned_dcommit and
+binned_dcommit_noinstall, with its level-wise round count.
 
 Two JSON lines:
   builds  --rounds interleaved rounds after one warm-up round, each on a fresh Scene: the host build's ms
@@ -72,7 +74,9 @@ def main():
         return s
 
     dev_arms = {"device": {}, "dcommit": {"commit": "device"}, "dcommit_noinstall": {"commit": "device", "install": False},
-                "ploc": {"build": "ploc"}, "ploc_dcommit": {"build": "ploc", "commit": "device"}}
+                "ploc": {"build": "ploc"}, "ploc_dcommit": {"build": "ploc", "commit": "device"},
+                "binned": {"build": "binned"}, "binned_dcommit": {"build": "binned", "commit": "device"},
+                "binned_dcommit_noinstall": {"build": "binned", "commit": "device", "install": False}}
     ctx = {a: drt.Renderer(0) for a in ("host", *dev_arms)}
     rows = {"host_build_ms": [], "host_upload_wall_ms": []}
     rows.update({f"{a}_{k}_ms": [] for a in dev_arms for k in ("build", "fetch", "commit", "upload_wall")})
@@ -107,7 +111,8 @@ def main():
     out["commit_info"] = {a: ctx[a].bvh_commit_info() for a in dev_arms}
     out["ploc_rounds"] = {k: ctx["ploc"].bvh_build_info()[k] for k in ("rounds", "forced_rounds")}
     out["ploc_radius"] = args.ploc_radius
-    out["sa_cost"] = {a: sa_cost(scenes[a].bvh_export()) for a in ("host", "device", "ploc")}
+    out["binned_rounds"] = ctx["binned"].bvh_build_info()["rounds"]
+    out["sa_cost"] = {a: sa_cost(scenes[a].bvh_export()) for a in ("host", "device", "ploc", "binned")}
     print(json.dumps(out), flush=True)
 
     arms = tuple(ctx)
@@ -141,6 +146,7 @@ def main():
         out["device"]["frame_ms"]["median"] / out["dcommit"]["frame_ms"]["median"], 3)
     out["ploc_over_device_frame_rate"] = round(out["device"]["frame_ms"]["median"] / out["ploc"]["frame_ms"]["median"], 3)
     out["ploc_radius"] = args.ploc_radius
+    out["binned_over_ploc_frame_rate"] = round(out["ploc"]["frame_ms"]["median"] / out["binned"]["frame_ms"]["median"], 3)
     print(json.dumps(out), flush=True)
     for r in ctx.values():
         r.close()
